@@ -1,7 +1,14 @@
 #!/usr/bin/env python3
 """Benchmark of the MI355X gravity + profile hot path (BASELINE.json configs 2-5).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times K steps of the headline workload below
+and prints the result line; --dump-outputs DIR also writes the potentials and
+accelerations of the last timed step as DIR/<name>.npy.  --full adds every
+other measurement and check after the timed steps: the precise-mode solve, the
+Barnes-Hut leg (config 5), the radial-profile size sweep (config 3), the
+API-level timings, the CPU baselines and the parity against the oracle.
 
 One step = one full direct-sum force + potential solve of a synthetic
 Plummer sphere whose positions / masses are already resident in HBM:
@@ -14,10 +21,11 @@ config 4), targets sharded across ranks, every rank sees all sources.
 Per-GPU target count is fixed ("weak" in particles); the pair count per
 GPU grows with N, which is why the metric is the whole-job pair rate.
 
-Printed (rank 0, one JSON line): metric/value in pairs/s, the roofline of
-the direct-sum kernel against the FP64 vector peak (achieved from HIP
-events on the library stream), and the CPU baseline (oracle restatement
-of direct.rs timed on a bounded target sample on this host).
+Printed (rank 0, one JSON line): metric/value in pairs/s, ms_per_step, the
+roofline of the direct-sum kernel against the FP64 vector peak (achieved
+from HIP events on the library stream) and, with --full, the other legs
+and the CPU baseline (oracle restatement of direct.rs timed on a bounded
+target sample on this host).
 """
 from __future__ import annotations
 
@@ -49,18 +57,57 @@ def parse():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--n-per-gpu", type=int, default=N_PER_GPU)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the potentials and accelerations of the last timed step as "
+                         "DIR/<name>.npy (float64; a fixed seeded sample of the particles when "
+                         "they exceed 64 MB)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything beside the headline: the "
+                         "precise-mode solve, the Barnes-Hut and radial-profile legs, the "
+                         "API-level timings, the CPU baselines and the parity checks (the "
+                         "options below pick among them)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0,
-                    help="target duration of the CPU-baseline sample")
+                    help="--full: target duration of the CPU-baseline sample")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-profile", action="store_true",
-                    help="skip the radial-profile leg (config 3)")
+                    help="--full: skip the radial-profile leg (config 3)")
     ap.add_argument("--profile-sizes", default="1000000,16000000,64000000,256000000",
-                    help="comma-separated particle counts of the profile size sweep")
-    ap.add_argument("--no-tree", action="store_true", help="skip the Barnes-Hut leg (config 5)")
+                    help="--full: comma-separated particle counts of the profile size sweep")
+    ap.add_argument("--no-tree", action="store_true",
+                    help="--full: skip the Barnes-Hut leg (config 5)")
     ap.add_argument("--no-api", action="store_true",
-                    help="skip the API-level (host arrays, H2D/D2H inclusive) direct-sum timing")
+                    help="--full: skip the API-level (host arrays, H2D/D2H inclusive) direct-sum "
+                         "timing")
     ap.add_argument("--tree-n", type=int, default=4_000_000)
     return ap.parse_args()
+
+
+DUMP_BYTES_MAX = 64 * 1000 * 1000  # --dump-outputs: all files of all ranks together
+DUMP_SEED = 20240
+
+
+def dump_outputs(out_dir: str, solver, rank: int, world: int) -> dict:
+    """Write what the timed path computed in its last step — this rank's
+    potentials and accelerations, as a caller of ShardedDirect.results()
+    receives them — to out_dir as float64 .npy files: pot.npy (n,) and
+    acc.npy (n, 3) on one rank, pot_rank<r>.npy / acc_rank<r>.npy on several.
+    32 bytes per particle; past DUMP_BYTES_MAX in all, only the rows of a
+    fixed sample of the particles are kept (sorted indices that depend on
+    nothing but n, the rank and DUMP_SEED)."""
+    pot, acc = solver.results()
+    n = len(pot)
+    keep = (DUMP_BYTES_MAX - 4096 * world) // (32 * world)
+    sampled = n > keep
+    if sampled:
+        idx = np.sort(np.random.default_rng(DUMP_SEED + rank).choice(n, size=keep, replace=False))
+        pot, acc = pot[idx], acc[idx]
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    tag = "" if world == 1 else f"_rank{rank}"
+    np.save(d / f"pot{tag}.npy", np.ascontiguousarray(pot, dtype=np.float64))
+    np.save(d / f"acc{tag}.npy", np.ascontiguousarray(acc, dtype=np.float64))
+    return {"dir": str(d), "files": [f"pot{tag}.npy", f"acc{tag}.npy"], "rows": len(pot),
+            "of": n, "sampled": bool(sampled)}
 
 
 class Dist:
@@ -982,19 +1029,24 @@ def main():
     elapsed = dist.max(t1 - t0)
     kernel_ms = [a.elapsed_ms(b) for a, b in events]
     kern_avg_ms = dist.max(float(np.mean(kernel_ms)))
+    dumped = None
+    if args.dump_outputs:  # the last timed step's results, before anything overwrites them
+        dumped = dump_outputs(args.dump_outputs, solver, rank, world)
 
-    # the same solve in precise mode (reference arithmetic, direct.rs:173-179:
-    # 1/r refined by a Newton step), kernel time only, beside the fast headline
-    with nat.precise_mode(True):
-        step(False)
-        pe = [(nat.Event(), nat.Event()) for _ in range(2)]
-        for a, b in pe:
-            solver.gather_sources()
-            a.record()
-            solver.solve()
-            b.record()
-        nat.synchronize()
-    precise_ms = dist.max(float(np.mean([a.elapsed_ms(b) for a, b in pe])))
+    precise_ms = None
+    if args.full:
+        # the same solve in precise mode (reference arithmetic, direct.rs:173-179:
+        # 1/r refined by a Newton step), kernel time only, beside the fast headline
+        with nat.precise_mode(True):
+            step(False)
+            pe = [(nat.Event(), nat.Event()) for _ in range(2)]
+            for a, b in pe:
+                solver.gather_sources()
+                a.record()
+                solver.solve()
+                b.record()
+            nat.synchronize()
+        precise_ms = dist.max(float(np.mean([a.elapsed_ms(b) for a, b in pe])))
 
     pairs_per_step = float(n_tot) * float(n_tot - 1)   # all ranks together
     value = pairs_per_step * args.steps / elapsed
@@ -1004,11 +1056,11 @@ def main():
     traffic, traffic_src = pmc_traffic("direct")
 
     tree = None
-    if not args.no_tree:
+    if args.full and not args.no_tree:
         tree = bench_tree(dist, args.tree_n, steps=max(3, args.steps), warmup=1,
                           cpu=not args.no_cpu_baseline, cpu_seconds=args.cpu_seconds)
     sweep = None
-    if not args.no_profile:
+    if args.full and not args.no_profile:
         # every rank: with N > 1 (or PBX_BENCH_FORCE_DIST=1) the sharded
         # profile with global edges (distributed radix select over RCCL)
         sizes = [int(s) for s in args.profile_sizes.split(",") if s]
@@ -1019,7 +1071,7 @@ def main():
                               cpu=not args.no_cpu_baseline and rank == 0 and world == 1,
                               dist=dist if dist.comm is not None else None)
     api = prof_api = None
-    if world == 1 and not args.no_api:
+    if args.full and world == 1 and not args.no_api:
         api = bench_api(pos, mass)
         if not args.no_profile:
             prof_api = bench_profile_api()
@@ -1027,7 +1079,7 @@ def main():
     if rank != 0:
         return
     cpu = None
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         cpu = cpu_rows(cpu_baseline(pos, mass, args.cpu_seconds),
                        cpu_baseline(pos, mass, args.cpu_seconds / 2, cores=1))
     out = {
@@ -1059,9 +1111,9 @@ def main():
             "unit": "TFLOP/s",
             "frac": achieved_tf / FP64_VECTOR_PEAK_TFLOPS,
             "traffic": traffic,
-            **{f"precise_{k}": v for k, v in precise_row(pairs_launch * FLOP_PER_PAIR,
-                                                          precise_ms).items()
-               if k in ("kernel_ms", "achieved", "frac")},
+            **({f"precise_{k}": v for k, v in precise_row(pairs_launch * FLOP_PER_PAIR,
+                                                           precise_ms).items()
+                if k in ("kernel_ms", "achieved", "frac")} if precise_ms is not None else {}),
             "traffic_source": traffic_src,
             "kernel": "sym_kernel<pot+acc> (each unordered pair once)" if solver.symmetric else "direct_kernel<Newtonian, pot+acc, self-skip>",
             "mode": "precise" if nat.get_precise() else "fast",
@@ -1078,7 +1130,10 @@ def main():
                               "issue peak (39.3e12/s)"},
         "cpu_baseline": cpu,
         "api_level": api,
+        "full": bool(args.full),
     }
+    if dumped is not None:
+        out["dumped_outputs"] = dumped
     if sweep is not None:
         head = sweep[0]
 
