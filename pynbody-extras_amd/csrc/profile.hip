@@ -2799,19 +2799,6 @@ struct GatherOut {
   uint32_t *rbase, *rn;   // per block: list start, deferred keys written
 };
 
-// exclusive sum of v[0 .. k) over a block (k <= blockDim.x)
-__device__ __forceinline__ uint32_t block_prefix(const uint32_t *__restrict__ v, int k,
-                                                 uint32_t *red) {
-  uint32_t x = (int)threadIdx.x < k ? v[threadIdx.x] : 0u;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-  if (lane_id() == 0) red[threadIdx.x >> 6] = x;
-  __syncthreads();
-  uint32_t t = 0;
-  for (int w = 0; w < (int)(blockDim.x >> 6); ++w) t += red[w];
-  return t;
-}
-
 // The speculative assignment's hand-over (select_tiles<FAM, true>): on a hit
 // (ctl->spec & SPEC_HIT) assign_hit only moves the select blocks' deferred
 // keys into their groups' segments and sums their slab rows; on a miss
@@ -3617,25 +3604,6 @@ __device__ bool grid_sync(uint64_t *bar, uint64_t gen, uint32_t nblk, int *ok) {
   }
   __syncthreads();
   return *ok != 0;
-}
-
-// A grid_sync arrival without the wait: keeps the counters at the
-// generation the host carries when a call skips a barrier it does not need
-// (every block skips it: the decision is grid-uniform).
-__device__ void grid_arrive(uint64_t *bar, uint64_t gen, uint32_t nblk) {
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const uint32_t g = blockIdx.x % 8, ngrp = nblk < 8 ? nblk : 8;
-    const uint64_t gs = nblk / 8 + (g < nblk % 8 ? 1 : 0);
-    const uint64_t old = __hip_atomic_fetch_add(bar + BAR_LINE * g, 1ull, __ATOMIC_RELAXED,
-                                                __HIP_MEMORY_SCOPE_AGENT);
-    if (old + 1 == gen * gs) {
-      const uint64_t o2 = __hip_atomic_fetch_add(bar + BAR_LINE * 8, 1ull, __ATOMIC_RELAXED,
-                                                 __HIP_MEMORY_SCOPE_AGENT);
-      if (o2 + 1 == gen * ngrp) st_sc1(bar + BAR_LINE * 9, gen);
-    }
-  }
 }
 
 struct MonoRec {  // a tile's selection result (phase 1)
@@ -4681,7 +4649,7 @@ struct Profile {
   bool mm_valid = false;   // mm = min / max key of x, cached on the host
   uint64_t mm[2] = {0, 0};
   MselState ms;
-  Buf msH, msR, msG, msNg, msM, msRows, msL0, msL1, msCnt, csrh, slabp, selst, accs;
+  Buf msH, msR, msG, msNg, msM, msRows, msL0, msL1, csrh, slabp, selst, accs;
   prim::HostBuf pin;  // pinned readback staging (async D2H, one sync)
   Buf x, w, idx, bins, perm, keys0, keys1, vtmp, hist, tsum, edges, counts, minmax, slab, acc,
       field, weight, ranks, bounds;
@@ -4767,18 +4735,6 @@ static void ensure_bins32(Profile &P, hipStream_t st) {
   P.bins_in8 = false;
 }
 
-// exclusive scan of len u32 in place
-static void scan_u32(Profile &P, hipStream_t st, uint32_t *a, int64_t len) {
-  prim::scan_u32(P.tsum, st, a, len);
-}
-
-// one stable radix pass: kin -> kout (+ values)
-template <typename K>
-static void radix_pass(Profile &P, hipStream_t st, const K *kin, const int32_t *vin, int vm,
-                       int64_t n, int shift, K *kout, int32_t *vout) {
-  prim::radix_pass<K>(P.hist, P.tsum, st, kin, vin, vm, n, shift, kout, vout);
-}
-
 static void check_n(int64_t n) {
   if (n < 0) fail(PBX_ERR_VALUE, "negative length");
   if (n >= (int64_t)1 << 31) fail(PBX_ERR_VALUE, "profiles are limited to < 2^31 particles");
@@ -4807,6 +4763,33 @@ static void minmax_of(Profile &P, hipStream_t st, uint64_t out[2]) {
   out[1] = P.mm[1];
 }
 
+// grid of the level-0 kernels (msel_hist0, fused_hist0, assign_gather, ...) over n_sel particles
+static int fused_grid(int64_t n_sel) {
+  return (int)std::min<int64_t>(256, std::max<int64_t>(1, n_sel / (MS0_TPB * 16)));
+}
+
+// the bin window [bin_min, bin_max] of bins.py:734-737 as key bounds
+struct KeyWindow {
+  uint64_t ka = 0ull, kb = ~0ull;
+  bool empty = false;  // a NaN bound keeps nothing
+};
+
+static KeyWindow key_window(int has_min, double bin_min, int has_max, double bin_max) {
+  KeyWindow w;
+  if (has_min || has_max) {
+    w.kb = ~0ull - 1;  // NaN keys never pass a comparison
+    if (has_min) {
+      if (bin_min != bin_min) w.empty = true;
+      else w.ka = dkey(bin_min);
+    }
+    if (has_max) {
+      if (bin_max != bin_max) w.empty = true;
+      else w.kb = std::min<uint64_t>(w.kb, dkey(bin_max));
+    }
+  }
+  return w;
+}
+
 // equaln edges by multi-rank radix select (see msel_* kernels).  Window and
 // rank semantics are those of the sort path: sorted_x[sorted_x >= bin_min],
 // then [sorted_x <= bin_max] (bins.py:734-737; NaN fails both and a NaN
@@ -4824,22 +4807,11 @@ static void msel_begin(Profile &P, int64_t nbins, int has_min, double bin_min, i
   S = MselState();
   S.nbins = nbins;
   S.nq = (int)nbins + 1;
-  bool empty = false;
-  uint64_t ka = 0ull, kb = ~0ull;
-  if (has_min || has_max) {
-    kb = ~0ull - 1;  // NaN keys never pass a comparison
-    if (has_min) {
-      if (bin_min != bin_min) empty = true;
-      else ka = dkey(bin_min);
-    }
-    if (has_max) {
-      if (bin_max != bin_max) empty = true;
-      else kb = std::min<uint64_t>(kb, dkey(bin_max));
-    }
-  }
+  const KeyWindow kw = key_window(has_min, bin_min, has_max, bin_max);
+  const uint64_t ka = kw.ka, kb = kw.kb;
   const uint64_t lo = std::max<uint64_t>(ka, kmin);
   const uint64_t hi = std::min<uint64_t>(kb, kmax);
-  if (empty || lo > hi) fail(PBX_ERR_VALUE, "index 0 is out of bounds for axis 0 with size 0");
+  if (kw.empty || lo > hi) fail(PBX_ERR_VALUE, "index 0 is out of bounds for axis 0 with size 0");
   const uint64_t span = hi - lo;
   S.B = span ? 64 - __builtin_clzll(span) : 1;
   S.L = 1;
@@ -4872,7 +4844,7 @@ static int64_t msel_hist(Profile &P, hipStream_t st, int level) {
   for (int l = 0; l <= level; ++l) s -= S.wd[l];
   if (level == 0) {
     PBX_HIP(hipMemsetAsync(H, 0, msel_hbytes(S), st));
-    const int g0 = (int)std::min<int64_t>(256, std::max<int64_t>(1, n / (MS0_TPB * 16)));
+    const int g0 = fused_grid(n);
     uint32_t *rows = (uint32_t *)P.msRows.get(sizeof(uint32_t) * (size_t)g0 * MS0_DIG);
     if (n) {
       ensure_x(P, st);
@@ -4942,8 +4914,9 @@ static void msel_edges_out(Profile &P, hipStream_t st, double *h_edges, int64_t 
   *n_edges = (m < 2) ? 2 : nq;
 }
 
-static void equaln_select(Profile &P, hipStream_t st, int64_t nbins, int has_min, double bin_min,
-                          int has_max, double bin_max, double *h_edges, int64_t *n_edges) {
+// every level of the radix select over this handle's x alone
+static void msel_levels(Profile &P, hipStream_t st, int64_t nbins, int has_min, double bin_min,
+                        int has_max, double bin_max) {
   uint64_t mm[2];
   minmax_of(P, st, mm);
   msel_begin(P, nbins, has_min, bin_min, has_max, bin_max, mm[0], mm[1]);
@@ -4951,6 +4924,11 @@ static void equaln_select(Profile &P, hipStream_t st, int64_t nbins, int has_min
     msel_hist(P, st, l);
     msel_resolve_level(P, st, l);
   }
+}
+
+static void equaln_select(Profile &P, hipStream_t st, int64_t nbins, int has_min, double bin_min,
+                          int has_max, double bin_max, double *h_edges, int64_t *n_edges) {
+  msel_levels(P, st, nbins, has_min, bin_min, has_max, bin_max);
   msel_edges_out(P, st, h_edges, n_edges);
 }
 
@@ -4983,37 +4961,37 @@ static void assign_device(Profile &P, hipStream_t st, const double *de, int64_t 
   P.csr_ready = false;
 }
 
-// stable counting sort of the bin ids (nb = dropped) carrying indices -> P.perm
-static void csr_device(Profile &P, hipStream_t st) {
-  const int64_t n = P.n, nb = P.nb;
-  if (P.csr_ready || !n) return;
-  ensure_bins32(P, st);
+// stable counting sort of n bin ids (nb = dropped) carrying indices -> P.perm
+// (n_dev: the kept count on the device, when the host has only the span n)
+static void csr_radix(Profile &P, hipStream_t st, int64_t n, int64_t nb, const int64_t *n_dev) {
   int bits = 0;
   while (((int64_t)1 << bits) <= nb) ++bits;
   uint32_t *ka = (uint32_t *)P.keys0.get(sizeof(uint32_t) * (size_t)n);
   uint32_t *kb = (uint32_t *)P.keys1.get(sizeof(uint32_t) * (size_t)n);
   int32_t *va = (int32_t *)P.perm.get(sizeof(int32_t) * (size_t)n);
   int32_t *vb = (int32_t *)P.vtmp.get(sizeof(int32_t) * (size_t)n);
-  const uint32_t *kin = (const uint32_t *)P.bins.p;
-  bool first = true;
   for (int shift = 0; shift < bits; shift += 8) {
     const bool last = shift + 8 >= bits;  // the sorted bin ids themselves are not needed
-    if (first && P.csrh_ready) {  // bins < 256: assign_bins counted the only pass
-      prim::radix_pass<uint32_t>(P.csrh, P.tsum, st, kin, nullptr, VAL_IOTA, n, shift,
-                                 last ? nullptr : ka, va, true);
-      P.csrh_ready = false;  // scanned in place: now offsets
-      first = false;
-    } else if (first) {
-      radix_pass<uint32_t>(P, st, kin, nullptr, VAL_IOTA, n, shift, last ? nullptr : ka, va);
-      first = false;
+    if (shift == 0) {  // bins < 256: assign_bins counted the only pass (csrh, scanned in place)
+      prim::radix_pass<uint32_t>(P.csrh_ready ? P.csrh : P.hist, P.tsum, st,
+                                 (const uint32_t *)P.bins.p, nullptr, VAL_IOTA, n, shift,
+                                 last ? nullptr : ka, va, P.csrh_ready, n_dev);
     } else {
-      radix_pass<uint32_t>(P, st, ka, va, VAL_ARRAY, n, shift, last ? nullptr : kb, vb);
+      prim::radix_pass<uint32_t>(P.hist, P.tsum, st, ka, va, VAL_ARRAY, n, shift,
+                                 last ? nullptr : kb, vb, false, n_dev);
       std::swap(ka, kb);
       std::swap(va, vb);
     }
   }
+  P.csrh_ready = false;
   if ((void *)va != P.perm.p)
     PBX_HIP(hipMemcpyAsync(P.perm.p, va, sizeof(int32_t) * n, hipMemcpyDeviceToDevice, st));
+}
+
+static void csr_device(Profile &P, hipStream_t st) {
+  if (P.csr_ready || !P.n) return;
+  ensure_bins32(P, st);
+  csr_radix(P, st, P.n, P.nb, nullptr);
   P.csr_ready = true;
 }
 
@@ -5035,50 +5013,70 @@ struct SelPrep {  // a selection's parameters and output buffers (select_prep)
   uint16_t *kpre = nullptr;
 };
 
+// a selection request as the entry points receive it
+struct SelectReq {
+  const void *pos = nullptr, *mass = nullptr;  // host or device arrays (on_device) of n particles
+  int64_t n = 0;
+  int on_device = 0, use_sphere = 0;
+  const double *sphere = nullptr;  // cx, cy, cz, R^2
+  const int64_t *fam = nullptr;    // nfam [lo, hi) slices
+  int nfam = 0, ndim = 3;
+  int pos_f32 = 0, mass_f32 = 0;
+};
+
+// the span [lo, hi) of n particles that holds every family member (no families: all)
+struct Span {
+  int64_t lo, hi;
+};
+
+static Span family_span(int64_t n, const int64_t *fam, int nfam) {
+  if (nfam <= 0) return {0, n};
+  int64_t lo = n, hi = 0;
+  for (int f = 0; f < nfam; ++f) {
+    const int64_t a = std::max<int64_t>(0, fam[2 * f]), b = std::min<int64_t>(n, fam[2 * f + 1]);
+    if (b > a) {
+      lo = std::min(lo, a);
+      hi = std::max(hi, b);
+    }
+  }
+  if (hi <= lo) lo = hi = 0;
+  return {lo, hi};
+}
+
 // parameters, host staging and output buffers of a selection (no launch)
-static SelPrep select_prep(Profile &P, hipStream_t st, const void *pos, const void *mass,
-                           int64_t n, int on_device, int use_sphere, const double *sphere,
-                           const int64_t *fam, int nfam, int ndim, bool lazy, int pos_f32,
-                           int mass_f32, bool tiled) {
+static SelPrep select_prep(Profile &P, hipStream_t st, const SelectReq &q, bool lazy, bool tiled) {
+  const int64_t n = q.n;
+  const int nfam = q.nfam, pos_f32 = q.pos_f32, mass_f32 = q.mass_f32;
   check_n(n);
-  if (ndim != 2 && ndim != 3) fail(PBX_ERR_VALUE, "ndim must be either 2 or 3");
+  if (q.ndim != 2 && q.ndim != 3) fail(PBX_ERR_VALUE, "ndim must be either 2 or 3");
   if (nfam < 0 || nfam > MAX_FAM) fail(PBX_ERR_VALUE, "at most %d family ranges", MAX_FAM);
   SelectParams sp{};
-  sp.use_sphere = use_sphere;
-  sp.ndim = ndim;
+  sp.use_sphere = q.use_sphere;
+  sp.ndim = q.ndim;
   sp.nfam = nfam;
-  if (use_sphere) {
-    sp.cx = sphere[0];
-    sp.cy = sphere[1];
-    sp.cz = sphere[2];
-    sp.r2max = sphere[3];
+  if (q.use_sphere) {
+    const double *s = q.sphere;
+    sp.cx = s[0];
+    sp.cy = s[1];
+    sp.cz = s[2];
+    sp.r2max = s[3];
     // (+0.0 or -0.0 centre: x - c == x for every x)
-    sp.sphere_origin = ndim == 3 && sphere[0] == 0.0 && sphere[1] == 0.0 && sphere[2] == 0.0;
+    sp.sphere_origin = q.ndim == 3 && s[0] == 0.0 && s[1] == 0.0 && s[2] == 0.0;
   }
-  int64_t lo = 0, hi = n;  // the span holding every family member
-  if (nfam > 0) {
-    lo = n;
-    hi = 0;
-    for (int f = 0; f < nfam; ++f) {
-      sp.fam_lo[f] = fam[2 * f];
-      sp.fam_hi[f] = fam[2 * f + 1];
-      const int64_t a = std::max<int64_t>(0, fam[2 * f]), b = std::min<int64_t>(n, fam[2 * f + 1]);
-      if (b > a) {
-        lo = std::min(lo, a);
-        hi = std::max(hi, b);
-      }
-    }
-    if (hi <= lo) lo = hi = 0;
+  for (int f = 0; f < nfam; ++f) {
+    sp.fam_lo[f] = q.fam[2 * f];
+    sp.fam_hi[f] = q.fam[2 * f + 1];
   }
+  const Span fsp = family_span(n, q.fam, nfam);
+  const int64_t lo = fsp.lo, hi = fsp.hi, span = hi - lo;
   sp.base = lo;
-  const int64_t span = hi - lo;
   if (lazy && (pos_f32 || mass_f32)) fail(PBX_ERR_VALUE, "the lazy selection takes float64 arrays");
   sp.mass_f32 = mass_f32;
   const size_t ps = pos_f32 ? sizeof(float) : sizeof(double);
   const size_t ms = mass_f32 ? sizeof(float) : sizeof(double);
-  const void *d_pos = pos, *d_mass = mass;
+  const void *pos = q.pos, *mass = q.mass, *d_pos = pos, *d_mass = mass;
   P.x_missing = false;
-  if (!on_device && n) {
+  if (!q.on_device && n) {
     // Only the families' span [lo, hi) is read: only it crosses PCIe, at its
     // own offset in an n-sized buffer (the kernels index particles
     // absolutely), through pinned chunks (h2d_staged).
@@ -5124,11 +5122,6 @@ static SelPrep select_prep(Profile &P, hipStream_t st, const void *pos, const vo
   return r;
 }
 
-// grid of the fused level-0 kernels (fused_hist0, assign_gather, ...) over n_sel particles
-static int fused_grid(int64_t n_sel) {
-  return (int)std::min<int64_t>(256, std::max<int64_t>(1, n_sel / (MS0_TPB * 16)));
-}
-
 struct TileHist {  // select_tiles' hinted level-0 histogram (null hint: none)
   const SelHint *hint = nullptr;
   bool cold = false;  // the hint slot holds no geometry yet (a first call): sample one
@@ -5141,13 +5134,10 @@ struct TileHist {  // select_tiles' hinted level-0 histogram (null hint: none)
   XSrc xs{};
 };
 
-static uint32_t select_launch(Profile &P, hipStream_t st, const void *pos, const void *mass,
-                              int64_t n, int on_device, int use_sphere, const double *sphere,
-                              const int64_t *fam, int nfam, int ndim, bool lazy = false,
-                              int pos_f32 = 0, int mass_f32 = 0, bool tiled = false,
-                              TileHist *th = nullptr) {
-  const SelPrep r = select_prep(P, st, pos, mass, n, on_device, use_sphere, sphere, fam, nfam, ndim,
-                                lazy, pos_f32, mass_f32, tiled);
+static uint32_t select_launch(Profile &P, hipStream_t st, const SelectReq &q, bool lazy = false,
+                              bool tiled = false, TileHist *th = nullptr) {
+  const SelPrep r = select_prep(P, st, q, lazy, tiled);
+  const int pos_f32 = q.pos_f32;
   const SelectParams &sp = r.sp;
   const uint32_t nt = r.nt;
   const int64_t hi = r.hi, span = r.span;
@@ -5423,8 +5413,8 @@ static void percentiles_device(Profile &P, hipStream_t st, int f_src, const doub
     // value key, 8 bits at a time (stable; first pass seeds the element ids)
     for (int shift = 0; shift < 64; shift += 8) {
       const bool last = shift + 8 >= 64;
-      radix_pass<uint64_t>(P, st, ka, shift == 0 ? nullptr : va, shift == 0 ? VAL_IOTA : VAL_ARRAY,
-                           n, shift, last ? nullptr : kb, vb);
+      prim::radix_pass<uint64_t>(P.hist, P.tsum, st, ka, shift == 0 ? nullptr : va,
+                                 shift == 0 ? VAL_IOTA : VAL_ARRAY, n, shift, last ? nullptr : kb, vb);
       std::swap(ka, kb);
       std::swap(va, vb);
     }
@@ -5438,7 +5428,7 @@ static void percentiles_device(Profile &P, hipStream_t st, int f_src, const doub
     while (((int64_t)1 << bits) <= nb) ++bits;
     for (int shift = 0; shift < bits; shift += 8) {
       const bool last = shift + 8 >= bits;
-      radix_pass<uint32_t>(P, st, ba, va, VAL_ARRAY, n, shift, last ? nullptr : bb, vb);
+      prim::radix_pass<uint32_t>(P.hist, P.tsum, st, ba, va, VAL_ARRAY, n, shift, last ? nullptr : bb, vb);
       std::swap(ba, bb);
       std::swap(va, vb);
     }
@@ -5492,48 +5482,45 @@ static uint32_t mono_max_tiles(int dev) {
   return (uint32_t)cache[(size_t)dev];
 }
 
-// the families' span of n particles (select_prep's rule)
-static int64_t family_span(int64_t n, const int64_t *fam, int nfam) {
-  if (nfam <= 0) return n;
-  int64_t lo = n, hi = 0;
-  for (int f = 0; f < nfam; ++f) {
-    const int64_t a = std::max<int64_t>(0, fam[2 * f]), b = std::min<int64_t>(n, fam[2 * f + 1]);
-    if (b > a) {
-      lo = std::min(lo, a);
-      hi = std::max(hi, b);
-    }
-  }
-  return hi > lo ? hi - lo : 0;
-}
+// The results pack of a radial call, in doubles:
+// [ctl][edges nq][counts nb][sums nsum][mapped: the tag | dist: this rank's counts nb]
+struct PackLayout {
+  static constexpr int NC = (int)(sizeof(FusedCtl) / sizeof(double));
+  static_assert(sizeof(FusedCtl) % sizeof(double) == 0, "FusedCtl packs as doubles");
+  int nq = 0, nb = 0, nsum = 0, nloc = 0;
+  PackLayout(int nq_, int nb_, int nsum_, bool dist) : nq(nq_), nb(nb_), nsum(nsum_), nloc(dist ? nb_ : 0) {}
+  int edges() const { return NC; }
+  int counts() const { return NC + nq; }
+  int sums() const { return NC + nq + nb; }
+  int ntot() const { return NC + nq + nb + nsum; }  // the packed words; the tag / local counts follow
+};
 
 // Runs the step as one launch when the selection fits (<= one tile per CU,
 // bins < 256, the fused sums in LDS); returns the pinned results pack
-// ([ctl][edges][counts][sums], the fused_pack layout) after ONE sync, or
-// null when the path does not apply or the call was discarded (a block gave
-// up at a barrier: the barrier words are reset and the caller runs the
-// multi-kernel path, which recomputes everything).
-static double *radial_mono_run(Profile &P, hipStream_t st, const void *pos, const void *mass,
-                               int64_t n, int on_device, int use_sphere, const double *sphere,
-                               const int64_t *fam, int nfam, int ndim, int64_t nbins, uint64_t ka,
-                               uint64_t kb, bool empty_bounds, const FusedStats &fs, int *nsum) {
-  check_n(n);
+// (PackLayout) after ONE sync, or null when the path does not apply or the
+// call was discarded (a block gave up at a barrier: the barrier words are
+// reset and the caller runs the multi-kernel path, which recomputes
+// everything).
+static double *radial_mono_run(Profile &P, hipStream_t st, const SelectReq &q, int64_t nbins,
+                               const KeyWindow &kw, const FusedStats &fs, int *nsum) {
+  check_n(q.n);
   const int nb = (int)nbins, nq = nb + 1, macc = fs.nm * nb;
-  if (nb >= RADIX || ndim < 2 || ndim > 3 || nfam < 0 || nfam > MAX_FAM) return nullptr;
+  if (nb >= RADIX || q.ndim < 2 || q.ndim > 3 || q.nfam < 0 || q.nfam > MAX_FAM) return nullptr;
   if (sizeof(double) * (size_t)macc + sizeof(uint32_t) * MONO_NW * RADIX > sizeof(uint16_t) * MONO_DIG)
     return nullptr;
-  const uint32_t nt = ntiles_of(family_span(n, fam, nfam));
+  const Span fsp = family_span(q.n, q.fam, q.nfam);
+  const uint32_t nt = ntiles_of(fsp.hi - fsp.lo);
   if (nt == 0 || nt > mono_max_tiles(P.device)) return nullptr;
-  const SelPrep r = select_prep(P, st, pos, mass, n, on_device, use_sphere, sphere, fam, nfam, ndim,
-                                /*lazy=*/true, 0, 0, /*tiled=*/false);
+  const SelPrep r = select_prep(P, st, q, /*lazy=*/true, /*tiled=*/false);
   const int64_t ns = std::max<int64_t>(r.span, 1);
   MonoArgs a{};
   a.pos = (const double *)r.d_pos;
   a.mass = (const double *)r.d_mass;
   a.n_hi = r.hi;
   a.sp = r.sp;
-  a.ka = ka;
-  a.kb = kb;
-  a.empty_bounds = empty_bounds ? 1 : 0;
+  a.ka = kw.ka;
+  a.kb = kw.kb;
+  a.empty_bounds = kw.empty ? 1 : 0;
   a.nb = nb;
   a.nq = nq;
   a.nbins = nbins;
@@ -5562,8 +5549,8 @@ static double *radial_mono_run(Profile &P, hipStream_t st, const void *pos, cons
   a.th = (uint32_t *)P.csrh.get(sizeof(uint32_t) * RADIX * (size_t)nt);
   a.slab = macc ? (double *)P.fslab.get(sizeof(double) * (size_t)nt * macc) : nullptr;
   a.counts = (unsigned long long *)P.counts.get(sizeof(uint64_t) * (size_t)(nb + 1));
-  constexpr int NC = (int)(sizeof(FusedCtl) / sizeof(double));
-  const int ntot = NC + nq + nb + macc;
+  const PackLayout L(nq, nb, macc, false);
+  const int ntot = L.ntot();
   // the pack lands in mapped host memory: the kernel's stores are the
   // readback (no copy on the stream), the host reads it after the sync
   double *hp = (double *)P.mpin.get(sizeof(double) * (size_t)(ntot + 1));
@@ -5617,7 +5604,7 @@ static double *radial_mono_run(Profile &P, hipStream_t st, const void *pos, cons
     const FusedCtl *hc = (const FusedCtl *)hp;
     P.bar_gen += (uint64_t)((hc->spec >> 8) & 0xff);
     if (hc->spec & SPEC_EDGE) ++P.n_mono_edge;
-    const double *he = hp + NC;
+    const double *he = hp + L.edges();
     P.medge_next = (int)P.mono_last_edges.size() == nq &&
                    std::memcmp(P.mono_last_edges.data(), he, sizeof(double) * nq) == 0;
     P.mono_last_edges.assign(he, he + nq);
@@ -5645,12 +5632,685 @@ static double *radial_mono_run(Profile &P, hipStream_t st, const void *pos, cons
   return hp;
 }
 
+// ------------------------------------ one-sync radial equaln: the host driver
+// pbx_profile_radial_equaln[_comm]: checks -> plan_stats -> radial_mono_run or
+// radial_multi_run (phases over one RadialCall) -> finish_call.
+// ---- the requested statistics -------------------------------------------
+constexpr int MAX_STATS = 16;
+struct StatReq {  // n (field, weight, columns) requests; sources 0 = x, 1 = weights, -1 = unweighted
+  int n;
+  const int *f_src, *w_src;
+  const uint32_t *cols;
+};
+
+static void check_stat_args(int64_t nbins, const StatReq &s) {
+  if (nbins < 1) fail(PBX_ERR_VALUE, "nbins must be >= 1");
+  if (nbins + 1 > MS_MAXQ) fail(PBX_ERR_VALUE, "the fused path supports nbins <= %d", MS_MAXQ - 1);
+  if (s.n < 0 || s.n > MAX_STATS) fail(PBX_ERR_VALUE, "at most 16 statistics");
+  for (int k = 0; k < s.n; ++k)
+    if (s.f_src[k] < 0 || s.f_src[k] > 1 || s.w_src[k] < -1 || s.w_src[k] > 1)
+      fail(PBX_ERR_VALUE, "the fused path takes the profile's x / weights only");
+}
+
+// one moments pass per request into accs + k * stride
+static void stat_moments(Profile &P, hipStream_t st, const StatReq &s, double *accs, int64_t stride) {
+  for (int k = 0; k < s.n; ++k)
+    moments_device(P, st, s.f_src[k], nullptr, P.field, s.w_src[k], nullptr, P.weight, s.cols[k],
+                   accs + k * stride);
+}
+
+// The reference's degenerate [s0, s0] (an equaln window of one key): one bin,
+// redone stepwise with 2 edges; then its read-back (the count from `counts`,
+// the sums) with one sync.
+static void one_bin_redo(Profile &P, hipStream_t st, double *h_edges, int build_csr,
+                         const StatReq &s, double *accs) {
+  h_edges[1] = h_edges[0];
+  double *de = (double *)P.edges.get(sizeof(double) * 2);
+  PBX_HIP(hipMemcpyAsync(de, h_edges, sizeof(double) * 2, hipMemcpyHostToDevice, st));
+  assign_device(P, st, de, 1);
+  if (build_csr) csr_device(P, st);
+  stat_moments(P, st, s, accs, NMOM);
+}
+
+static void one_bin_out(hipStream_t st, const StatReq &s, const double *accs, const void *counts,
+                        int64_t *h_counts, double *h_moments) {
+  PBX_HIP(hipMemcpyAsync(h_counts, counts, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+  if (s.n)
+    PBX_HIP(hipMemcpyAsync(h_moments, accs, sizeof(double) * s.n * NMOM, hipMemcpyDeviceToHost, st));
+  PBX_HIP(hipStreamSynchronize(st));
+}
+
+// The fused sums of a call: the distinct monomials (x^a w^b |x|^c |w|^d) of
+// the requested columns, accumulated inside the assignment pass.  fs.nm == 0:
+// not fused (no statistics, or more than AS_MAXM / the LDS budget's distinct
+// sums: separate moment passes).
+struct StatPlan {
+  FusedStats fs{};
+  int slot[MAX_STATS * NMOM];  // [stat][column] -> monomial; -1 = column not accumulated (0)
+};
+
+static StatPlan plan_stats(const StatReq &s, int64_t nb) {
+  StatPlan p;
+  FusedStats &fs = p.fs;
+  std::fill(p.slot, p.slot + MAX_STATS * NMOM, -1);
+  uint32_t mkey[AS_MAXM];  // the monomial of slot j, as packed powers
+  bool fuse = s.n > 0;
+  for (int k = 0; k < s.n && fuse; ++k)
+    for (int c = 0; c < NMOM; ++c) {
+      if (!((s.cols[k] >> c) & 1u)) continue;
+      const bool wc = (c == 0 || c == 1 || c == 2 || c == 5);
+      if (wc && s.w_src[k] < 0) continue;  // unweighted: the weighted columns stay 0
+      uint32_t e[4] = {0, 0, 0, 0};        // powers of x, w, |x|, |w|
+      const int fp = (c == 2 || c == 4) ? 2 : (c == 0 ? 0 : 1);
+      const bool fa = (c == 5 || c == 6);
+      e[(fa ? 2 : 0) + s.f_src[k]] += fp;
+      if (wc) e[s.w_src[k]] += 1;
+      const uint32_t key = e[0] | e[1] << 4 | e[2] << 8 | e[3] << 12;
+      int slot = -1;
+      for (int j = 0; j < fs.nm; ++j)
+        if (mkey[j] == key) slot = j;
+      if (slot < 0) {
+        if (fs.nm == AS_MAXM || (int64_t)(fs.nm + 1) * nb > 2 * LDS_MOM_BINS * NMOM) {
+          fuse = false;
+          break;
+        }
+        slot = fs.nm++;
+        mkey[slot] = key;
+        fs.f[slot] = s.f_src[k];
+        fs.w[slot] = s.w_src[k];
+        fs.col[slot] = c;
+        fs.op[slot] = key == 0x010u ? MO_W : key == 0x001u ? MO_X : key == 0x011u ? MO_XW
+                    : key == 0x012u ? MO_XXW : key == 0x002u ? MO_XX : key == 0x020u ? MO_WW
+                    : MO_GEN;
+      }
+      p.slot[k * NMOM + c] = slot;
+    }
+  if (!fuse) fs.nm = 0;
+  return p;
+}
+
+// plan_stats' inverse: the packed monomial sums [slot][bin] into [stat][bin][column]
+static void expand_sums(const StatPlan &p, int n_stats, int64_t nb, const double *sums,
+                        double *h_moments) {
+  for (int k = 0; k < n_stats; ++k)
+    for (int64_t b = 0; b < nb; ++b)
+      for (int c = 0; c < NMOM; ++c) {
+        const int slot = p.slot[k * NMOM + c];
+        h_moments[(k * nb + b) * NMOM + c] = slot < 0 ? 0.0 : sums[slot * nb + b];
+      }
+}
+
+// ---- the multi-kernel path ----------------------------------------------
+struct AssignOut {  // what an assignment back end leaves for the finish and the pack
+  double *maccs = nullptr;   // the sums' per-block rows (ablocks of them), summed inside the pack
+  double *maccs2 = nullptr;  // tiled: fix_deferred's rows (g0 of them)
+  uint32_t ablocks = 0;
+  const uint32_t *cnt_offs = nullptr;  // scanned CSR histogram the counts come from (null: P.counts)
+  bool csr_pack = false;               // tiled: csr_slots is launched with the pack
+  uint32_t *th = nullptr;              // tiled: the [tile][bin] histogram, the bins by particle
+  uint8_t *bins8 = nullptr;            // slot, the deferred keys' lists
+  GatherOut go{};
+  SpecIO sio{};
+};
+
+// One multi-kernel call: the request, then what each phase leaves for the
+// next.  radial_multi_run runs the phases in stream order.
+struct RadialCall {
+  Profile &P;
+  hipStream_t st;
+  void *comm;                        // null: one rank
+  std::unique_lock<std::mutex> &lk;  // (released inside comm_allreduce's host wait)
+  const CommRanks cr;
+  const bool dist;
+  const int64_t nb;  // bins requested; nq ranks (edges)
+  const int nq;
+  const bool lazy;  // bins < 256: the lazy selection + tile-walking assignment / CSR passes
+  const uint64_t ka, kb;
+  const bool empty_bounds;
+  const FusedStats fs;
+  const int build_csr;
+  // select
+  SelHint *hints = nullptr;
+  TileHist thist;
+  uint32_t nt = 0;
+  bool tiled = false;   // x by tile (large inputs): tile offsets from fused_hist0
+  bool hinted = false;  // ... and select_tiles built the level-0 histogram
+  // level 0
+  int64_t n_sel = 0;  // tiled particles (the families' span)
+  int g0 = 0;
+  bool agath = false;  // assignment fused with the gather (assign_tiles)
+  uint32_t nab = 0;    // ... its workgroups (at_blocks: one per select block + 1)
+  uint64_t *stat = nullptr;
+  FusedCtl *ctl = nullptr;
+  unsigned long long *cnt = nullptr;
+  uint32_t *H = nullptr, *rows = nullptr, *bcnt = nullptr;
+  const double *x = nullptr;
+  // resolve
+  MsRank *R = nullptr;
+  uint32_t *gdig = nullptr, *goff = nullptr, *gq = nullptr, *boff = nullptr, *bins = nullptr;
+  SpecTab *stab = nullptr;
+  int64_t n_global = 0, seg_total = 0;  // dist: kept particles / group-segment keys over all ranks
+  uint64_t *seg = nullptr;
+  double *de = nullptr;
+
+  RadialCall(Profile &P_, hipStream_t st_, void *comm_, std::unique_lock<std::mutex> &lk_,
+             CommRanks cr_, int64_t nbins, const KeyWindow &kw, const FusedStats &fs_, int csr)
+      : P(P_), st(st_), comm(comm_), lk(lk_), cr(cr_), dist(comm_ != nullptr), nb(nbins),
+        nq((int)nbins + 1), lazy(nbins < RADIX), ka(kw.ka), kb(kw.kb), empty_bounds(kw.empty),
+        fs(fs_), build_csr(csr) {}
+
+  void select(const SelectReq &q);
+  void level0();
+  void resolve();
+  AssignOut assign_tiled();
+  void gather();
+  void finish(const AssignOut &a);
+  AssignOut assign_lazy();
+  AssignOut assign_eager();
+  double *pack(const AssignOut &a, int *nsum_out);
+};
+
+// Hint and speculation set-up, the selection, the global key range (dist).
+inline void RadialCall::select(const SelectReq &q) {
+  ++P.n_multi;
+  // one rank, lazy: the level-0 histogram of a tiled selection is built by
+  // select_tiles with the previous tiled call's geometry (slot n_tiled & 1;
+  // fused_hist0 writes this call's into the other slot)
+  if (!dist && lazy && !P.hint_off) {
+    if (!P.shint.p) {
+      P.shint.get(2 * sizeof(SelHint));
+      PBX_HIP(hipMemsetAsync(P.shint.p, 0, 2 * sizeof(SelHint), st));
+    }
+    hints = (SelHint *)P.shint.p;
+  }
+  thist.hint = hints ? hints + (P.n_tiled & 1) : nullptr;
+  thist.cold = hints && P.n_tiled == 0;  // (no earlier tiled call left a geometry)
+  thist.ka = ka;
+  thist.kb = empty_bounds ? 0ull : kb;
+  // the speculative assignment: when the last tiled call's level-0 ranks
+  // matched the stored table (a repeated or similar call), select_tiles
+  // bins with it (checked by fused_resolve; a miss takes assign_tiles).
+  // It stores no x, which is then rebuilt from the positions on demand:
+  // only from positions the handle owns (staged host arrays) or that the
+  // caller declared stable
+  bool spec_ops = true;  // select_tiles' sums take the dedicated monomials only
+  for (int k = 0; k < fs.nm; ++k) spec_ops = spec_ops && fs.op[k] != MO_GEN;
+  if (hints && P.spec_next && P.stab.p && nb <= SPEC_MAXB && fs.nm * nb <= SPEC_MACC && spec_ops &&
+      (!q.on_device || P.src_stable)) {
+    thist.sa.tab = (const SpecTab *)P.stab.p;
+    thist.sa.fs = fs;
+    thist.sa.nb = (int)nb;
+    thist.sa.edge = P.edge_next ? 1 : 0;
+    if (thist.sa.edge && !P.slteq.p) {  // (zero before the first use; fused_resolve re-zeroes)
+      P.slteq.get(sizeof(uint32_t) * 2 * MS_MAXQ);
+      PBX_HIP(hipMemsetAsync(P.slteq.p, 0, sizeof(uint32_t) * 2 * MS_MAXQ, st));
+    }
+    thist.sa.lteq = (uint32_t *)P.slteq.p;
+    if (P.spec_dirty) {
+      if (P.sflag.p) PBX_HIP(hipMemsetAsync(P.sflag.p, 0, sizeof(uint32_t), st));
+      if (P.slteq.p) PBX_HIP(hipMemsetAsync(P.slteq.p, 0, sizeof(uint32_t) * 2 * MS_MAXQ, st));
+      P.spec_dirty = false;
+    }
+  }
+  nt = select_launch(P, st, q, lazy, /*tiled=*/true, &thist);
+  if (thist.spec) {
+    ++P.n_spec;
+    P.spec_dirty = true;  // (until the call's results arrive)
+  }
+  tiled = P.x_tiled;
+  hinted = hints && tiled;
+  if (hinted) ++P.n_tiled;  // (the next tiled call reads the slot this one writes)
+  if (dist)  // global key range: every min / max slot pair (~min, max) max-reduced
+    comm_allreduce(comm, (uint64_t *)P.selst.p + nt + 1, (uint64_t *)P.selst.p + nt + 1,
+                   2 * MM_SLOTS, 2, 2, st, lk);
+}
+
+// Level 0: the control block and this rank's digit histogram (rows -> H).
+inline void RadialCall::level0() {
+  n_sel = nt ? P.sel_span : 0;
+  stat = (uint64_t *)P.selst.p;
+  ctl = (FusedCtl *)P.fctl.get(sizeof(FusedCtl));
+  cnt = (unsigned long long *)P.counts.get(sizeof(uint64_t) * (size_t)(nb + 1));
+  H = (uint32_t *)P.msH.get(sizeof(uint32_t) * MS0_DIG);
+  x = (const double *)P.x.p;
+  g0 = fused_grid(n_sel);
+  rows = (uint32_t *)P.msRows.get(sizeof(uint32_t) * (size_t)g0 * MS0_DIG);
+  // tiled selections: assignment fused with the gather (assign_tiles),
+  // the deferred keys binned block by block by fix_deferred; the three
+  // per-block words [bcnt | rbase | rn] zeroed by fused_hist0
+  agath = tiled && lazy && n_sel;
+  if (agath && g0 < 2) fail(PBX_ERR_RUNTIME, "tiled selection with one level-0 block");
+  nab = agath ? at_blocks(g0) : 0u;
+  bcnt = agath ? (uint32_t *)P.fblk.get(sizeof(uint32_t) * 3 * (size_t)nab) : nullptr;
+  const uint32_t *hflag = (const uint32_t *)(stat + nt + 1 + 2 * MM_SLOTS);
+  const FusedSetup fsu{(const uint64_t *)stat, nt, n_sel, ka, kb, (int)empty_bounds, (int)tiled,
+                       (uint32_t *)P.toff.p, bcnt, agath ? 3 * (int)nab : 0, (int)dist,
+                       (const uint64_t *)P.kw.p,
+                       hinted ? hints + ((P.n_tiled - 1) & 1) : nullptr, hflag,
+                       hinted ? hints + (P.n_tiled & 1) : nullptr, (const uint32_t *)P.sbt.p,
+                       thist.spec ? (const uint32_t *)thist.sa.flag : nullptr, thist.xs};
+  hipLaunchKernelGGL(fused_hist0, dim3(g0), dim3(MS0_TPB), 0, st, x, fsu, ctl, cnt, (int)nb, rows);
+  hipLaunchKernelGGL(msel_reduce0h, dim3(MS0_DIG / R0_DIG), dim3(MS0_TPB), 0, st,
+                     (const uint32_t *)rows, g0, hinted ? (const uint32_t *)P.srows.p : nullptr,
+                     hinted ? SH_K * (g0 - 1) * (int)P.sel_rsub : 0, (const int32_t *)&ctl->hint, H,
+                     stat + nt, 2 + 2 * MM_SLOTS);
+  PBX_HIP(hipGetLastError());
+  P.sel_tail_zero = stat + nt;  // (select_launch: no fill before the next tiled call)
+}
+
+// Resolve: the ranks' level-0 digits and groups, the per-block segment
+// offsets; dist: the global histogram and counts, each rank's slice of the
+// global segments, and the call's one extra read-back (the segment length).
+inline void RadialCall::resolve() {
+  int64_t *gsc = nullptr;  // dist: [global kept count][ctl copy]
+  uint32_t *lc_all = nullptr;
+  if (dist) {
+    gsc = (int64_t *)P.dscal.get(sizeof(int64_t) * 4 + sizeof(FusedCtl));
+    lc_all = (uint32_t *)P.dlc.get(sizeof(uint32_t) * (size_t)cr.nranks * MS_MAXQ);
+    PBX_HIP(hipMemsetAsync(lc_all, 0, sizeof(uint32_t) * (size_t)cr.nranks * MS_MAXQ, st));
+    // [global kept count, ranks whose look-back failed]
+    hipLaunchKernelGGL(dist_status, dim3(1), dim3(1), 0, st, (const FusedCtl *)ctl, gsc + 2);
+    comm_allreduce(comm, gsc + 2, gsc, 2, 1, 0, st, lk);
+    comm_allreduce(comm, H, H, MS0_DIG, 3, 0, st, lk);
+  }
+  R = (MsRank *)P.msR.get(sizeof(MsRank) * (size_t)nq);
+  // [gdig | goff | gq | boff: a row per assignment workgroup (g0 or nab rows)]
+  gdig = (uint32_t *)P.fgrp.get(sizeof(uint32_t) * (3 + (size_t)std::max<uint32_t>(g0, nab)) *
+                                (MS_MAXQ + 1));
+  goff = gdig + (MS_MAXQ + 1);
+  gq = goff + (MS_MAXQ + 1);
+  boff = gq + (MS_MAXQ + 1);
+  // the stored bin table (one rank, tiled assignment): allocated zeroed (invalid)
+  if (agath && !dist) {
+    if (!P.stab.p) {
+      P.stab.get(sizeof(SpecTab));
+      PBX_HIP(hipMemsetAsync(P.stab.p, 0, sizeof(SpecTab), st));
+    }
+    stab = (SpecTab *)P.stab.p;
+  }
+  hipLaunchKernelGGL(fused_resolve, dim3(nq), dim3(FR_TPB), 0, st, (const uint32_t *)H, ctl, nb, nq,
+                     R, gdig, goff, gq, (const uint32_t *)rows, g0, boff, bcnt,
+                     dist ? lc_all + (size_t)cr.rank * MS_MAXQ : nullptr,
+                     (const uint32_t *)P.srows.p, P.sel_rsub, (const SpecTab *)stab,
+                     thist.spec ? thist.sa.flag : nullptr, (int)nb,
+                     (thist.spec && thist.sa.edge) ? thist.sa.lteq : nullptr);
+  if (dist) {
+    comm_allreduce(comm, lc_all, lc_all, (int64_t)cr.nranks * MS_MAXQ, 3, 0, st, lk);
+    hipLaunchKernelGGL(dist_rank_offsets, dim3(nq), dim3(TPB), 0, st, (const FusedCtl *)ctl,
+                       (const uint32_t *)lc_all, cr.rank, g0, boff);
+    PBX_HIP(hipGetLastError());
+    FusedCtl *hc = (FusedCtl *)P.pin.get(sizeof(FusedCtl) + 16);
+    int64_t *hn = (int64_t *)(hc + 1);
+    PBX_HIP(hipMemcpyAsync(hc, ctl, sizeof(FusedCtl), hipMemcpyDeviceToHost, st));
+    PBX_HIP(hipMemcpyAsync(hn, gsc, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    PBX_HIP(hipStreamSynchronize(st));
+    n_global = hn[0];
+    if (hn[1])  // (every rank sees the same sum: all fail here, no rank left in a collective)
+      fail(PBX_ERR_RUNTIME, "selection look-back did not complete (%lld of %d ranks)",
+           (long long)hn[1], cr.nranks);
+    seg_total = (hc->err & 2) ? 0 : hc->total;
+    if (n_global >= (int64_t)1 << 32)  // (every rank sees the same count: all fail here)
+      fail(PBX_ERR_VALUE, "distributed equaln over %lld particles: the u32 digit "
+           "histograms hold at most 2**32 - 1", (long long)n_global);
+  }
+  seg = (uint64_t *)P.fseg.get(
+      sizeof(uint64_t) * (size_t)std::max<int64_t>(1, std::max<int64_t>(n_sel, seg_total)));
+  if (seg_total) PBX_HIP(hipMemsetAsync(seg, 0, sizeof(uint64_t) * (size_t)seg_total, st));
+  de = (double *)P.edges.get(sizeof(double) * (size_t)nq);
+  bins = (uint32_t *)P.bins.get(sizeof(uint32_t) * (size_t)(n_sel ? n_sel : 1));
+  P.bins_in8 = agath;
+  P.csrh_ready = false;
+}
+
+// Tiled back end, before the edges exist: assign_tiles gathers the group
+// keys and bins every key whose bin its level-0 digit decides; the others are
+// deferred to fix_deferred (finish).
+inline AssignOut RadialCall::assign_tiled() {
+  AssignOut a;
+  const int nr = (int)nb + 1;
+  const int64_t macc = (int64_t)fs.nm * nb;
+  a.th = (uint32_t *)P.csrh.get(sizeof(uint32_t) * (size_t)nt * nr);
+  a.bins8 = (uint8_t *)P.bins8.get((size_t)nt * TILE);  // by particle slot
+  // (nab: assign_tiles' workgroups = its slab rows)
+  double *slab = fs.nm ? (double *)P.fslab.get(sizeof(double) * (size_t)(nab + g0) * macc) : nullptr;
+  a.go = GatherOut{seg, (AgRec *)P.frec.get(sizeof(AgRec) * (size_t)n_sel), bcnt, bcnt + nab,
+                   bcnt + 2 * nab};
+  a.sio = SpecIO{stab, thist.spec ? thist.sa.rec : nullptr,
+                 thist.spec ? (const uint32_t *)thist.sa.rbase : nullptr,
+                 thist.spec ? (const uint32_t *)thist.sa.rn : nullptr,
+                 thist.spec ? (const double *)thist.sa.slab : nullptr};
+  if (thist.spec) {
+    // a speculating call: the hit's hand-over (assign_hit), and x from the
+    // positions for a miss whose selection stored none (xsrc_miss); each
+    // returns at once unless the call is its case
+    constexpr uint32_t xpb = 4;
+    hipLaunchKernelGGL(xsrc_miss, dim3(ceil_div(nt, xpb)), dim3(TPB), 0, st, (const FusedCtl *)ctl,
+                       thist.xs, nt, xpb);
+    if (fs.nm)
+      hipLaunchKernelGGL(assign_hit<true>, dim3(g0), dim3(MS0_TPB), 0, st, (const FusedCtl *)ctl,
+                         (const uint32_t *)gdig, (const uint32_t *)boff, (int)nb, fs, slab, a.go, a.sio);
+    else
+      hipLaunchKernelGGL(assign_hit<false>, dim3(g0), dim3(MS0_TPB), 0, st, (const FusedCtl *)ctl,
+                         (const uint32_t *)gdig, (const uint32_t *)boff, (int)nb, fs, slab, a.go, a.sio);
+  }
+  // the sums' form: {Σw, Σx·w} / {Σw} as dedicated adds, else any monomials
+  const int mm = (fs.nm == 2 && fs.op[0] == MO_W && fs.op[1] == MO_XW) ? 1
+                 : (fs.nm == 1 && fs.op[0] == MO_W) ? 2 : 0;
+  const size_t lds = sizeof(double) * (size_t)macc + sizeof(uint32_t) * (size_t)(nr | 1) * AT_TR;
+  auto at = [&](auto kern) {
+    hipLaunchKernelGGL(kern, dim3(nab), dim3(AT_BT), lds, st, x, (const uint64_t *)P.kw.p,
+                       P.sel_base, P.sel_span, nt, P.sel_mass, (const FusedCtl *)ctl, ka, kb,
+                       (const MsRank *)R, nq, (const uint32_t *)gdig, boff, (int)nb, a.bins8, a.th, fs,
+                       slab, a.go, stab, g0);
+  };
+  if (!fs.nm) at(assign_tiles<false, 0>);
+  else if (mm == 1) at(assign_tiles<true, 1>);
+  else if (mm == 2) at(assign_tiles<true, 2>);
+  else at(assign_tiles<true, 0>);
+  PBX_HIP(hipGetLastError());
+  a.ablocks = nab;
+  if (fs.nm) {
+    a.maccs = slab;
+    a.maccs2 = slab + (size_t)nab * macc;
+  }
+  a.cnt_offs = a.th;       // (scanned by finish)
+  a.csr_pack = build_csr;  // the CSR pass (csr_slots) is launched with the pack: its first blocks carry it
+  return a;
+}
+
+// The other back ends assign after the edges: the group keys alone.
+inline void RadialCall::gather() {
+  hipLaunchKernelGGL(fused_gather, dim3(g0), dim3(MS0_TPB), 0, st, x, ka, kb, (const FusedCtl *)ctl,
+                     (const uint32_t *)gdig, (const uint32_t *)boff, seg,
+                     tiled ? (const uint64_t *)P.kw.p : nullptr, nt);
+}
+
+// Finish: every rank's group keys (dist), the edges; tiled: the deferred
+// keys' bins and the scan of the [tile][bin] histogram.
+inline void RadialCall::finish(const AssignOut &a) {
+  if (dist)  // every rank's group keys, each in its own slice: the all-gather
+    comm_allreduce(comm, seg, seg, seg_total, 2, 0, st, lk);
+  hipLaunchKernelGGL(fused_finish, dim3(nq), dim3(FR_TPB), 0, st, (const FusedCtl *)ctl,
+                     (const MsRank *)R, (const uint32_t *)gq, (const uint32_t *)goff,
+                     (const uint64_t *)seg, de, (const SpecTab *)stab, nq,
+                     thist.spec ? thist.sa.flag : nullptr,
+                     (thist.spec && thist.sa.edge) ? thist.sa.lteq : nullptr);
+  PBX_HIP(hipGetLastError());
+  if (!agath) return;
+  const uint32_t nr = (uint32_t)nb + 1;
+  const size_t lds = sizeof(double) * ((size_t)fs.nm * nb + nb + 1) + sizeof(uint32_t) * FD_LDSW;
+  auto fd = [&](auto kern) {
+    hipLaunchKernelGGL(kern, dim3(g0), dim3(MS0_TPB), lds, st, (const FusedCtl *)ctl,
+                       (const AgRec *)a.go.rec, (const uint32_t *)a.go.rbase,
+                       (const uint32_t *)a.go.rn, (const double *)de, (const uint32_t *)gq, (int)nb,
+                       a.bins8, a.th, nt, fs, a.maccs2, a.sio);
+  };
+  if (fs.nm) fd(fix_deferred<true>);
+  else fd(fix_deferred<false>);
+  PBX_HIP(hipGetLastError());
+  // (a row-wise scan — one block per bin row, its base from row totals
+  // summed by assign_gather / fix_deferred — took 15-16 us against this
+  // one-pass look-back scan's 11 us at 64M: dropped)
+  prim::scan_u32(P.tsum, st, a.th, (int64_t)nt * nr);
+}
+
+// Lazy back end (bins < 256, not tiled by block): the tile-walking
+// assignment over the lazy selection + its CSR pass.
+inline AssignOut RadialCall::assign_lazy() {
+  AssignOut a;
+  const int64_t macc = (int64_t)fs.nm * nb;
+  const bool ldse = (nb + 1) <= LDS_EDGES;
+  const size_t lds = sizeof(double) * (size_t)macc + (ldse ? sizeof(double) * (nb + 1) : 0);
+  uint32_t *th = (uint32_t *)P.csrh.get(sizeof(uint32_t) * (size_t)nt * RADIX);
+  const uint32_t tpbk = std::min<uint32_t>(AS_TILES, std::max<uint32_t>(1, nt / 1024));
+  a.ablocks = ceil_div(nt, tpbk);
+  double *slab = fs.nm ? (double *)P.fslab.get(sizeof(double) * (size_t)a.ablocks * macc) : nullptr;
+  const uint64_t *kwp = (const uint64_t *)P.kw.p;
+  const uint32_t *tof = (const uint32_t *)P.toff.p;
+  // few tiles: one tile per 1024-thread block, every wave a piece of it
+  const bool wide = tpbk == 1 && nt < 1024;
+  auto go = [&](auto kern, int bt) {
+    hipLaunchKernelGGL(kern, dim3(a.ablocks), dim3(bt), lds, st, x, kwp, tof, P.sel_base, nt, tpbk,
+                       P.sel_mass, (const double *)de, (int)nb, bins, th, fs, slab, tiled ? 1 : 0);
+  };
+  auto sel = [&](auto bt) {
+    constexpr int BT = decltype(bt)::value;
+    if (fs.nm) ldse ? go(assign_sel<true, true, BT>, BT) : go(assign_sel<true, false, BT>, BT);
+    else ldse ? go(assign_sel<false, true, BT>, BT) : go(assign_sel<false, false, BT>, BT);
+  };
+  if (wide) sel(std::integral_constant<int, 1024>{});
+  else sel(std::integral_constant<int, TPB>{});
+  PBX_HIP(hipGetLastError());
+  if (fs.nm) a.maccs = slab;
+  // the counts are row-start differences of the scanned [bin][tile] table
+  prim::scan_u32(P.tsum, st, th, (int64_t)nt * RADIX);
+  a.cnt_offs = th;
+  if (build_csr) {
+    int32_t *perm = (int32_t *)P.perm.get(sizeof(int32_t) * (size_t)n_sel);
+    hipLaunchKernelGGL(csr_sel<uint32_t>, dim3(nt), dim3(TPB), 0, st, tof, &ctl->n,
+                       (const uint32_t *)bins, (const uint32_t *)th, nt, perm, (uint32_t)RADIX);
+    PBX_HIP(hipGetLastError());
+  }
+  return a;
+}
+
+// Eager back end (bins >= 256): assign_bins over the compacted x + the
+// radix CSR, both with the device's kept count.
+inline AssignOut RadialCall::assign_eager() {
+  AssignOut a;
+  const int64_t *n_dev = &ctl->n;
+  const int64_t macc = (int64_t)fs.nm * nb;
+  size_t lds = sizeof(double) * (size_t)macc +
+               ((nb + 1) <= LDS_EDGES ? sizeof(double) * (nb + 1) : 0) + sizeof(uint32_t) * (nb + 1);
+  if (lds > 150 * 1024) fail(PBX_ERR_VALUE, "too many bins for the device histogram (%lld)", (long long)nb);
+  uint32_t *th = (nb < RADIX) ? (uint32_t *)P.csrh.get(sizeof(uint32_t) * (size_t)nt * RADIX)
+                              : nullptr;
+  const uint32_t tpbk = std::min<uint32_t>(AS_TILES, std::max<uint32_t>(1, nt / 1024));
+  a.ablocks = ceil_div(nt, tpbk);
+  double *slab = fs.nm ? (double *)P.fslab.get(sizeof(double) * (size_t)a.ablocks * macc) : nullptr;
+  // with the CSR pass, the bin counts are differences of its scanned
+  // [bin][tile] histogram: no global count atomics in assign_bins
+  if (th && build_csr) a.cnt_offs = th;
+  unsigned long long *acnt = a.cnt_offs ? nullptr : cnt;
+  if (fs.nm)
+    launch_assign<true>(a.ablocks, lds, st, x, n_sel, (const double *)de, (int)nb, bins, acnt, th, nt,
+                        tpbk, n_dev, (const double *)P.w.p, fs, slab);
+  else
+    launch_assign<false>(a.ablocks, lds, st, x, n_sel, (const double *)de, (int)nb, bins, acnt, th, nt,
+                         tpbk, n_dev, nullptr, fs, nullptr);
+  PBX_HIP(hipGetLastError());
+  P.csrh_ready = th != nullptr;
+  if (fs.nm) a.maccs = slab;  // its rows are summed inside fused_pack
+  if (build_csr) csr_radix(P, st, n_sel, nb, n_dev);  // (the device has the kept count)
+  return a;
+}
+
+// The results packed into one block (PackLayout).  One rank: it lands in
+// mapped host memory with a completion tag (no D2H copy, no stream sync).
+// dist: a device block, all-reduced (every rank packs the fused sums'
+// columns, zeros without particles, so the regions have the same length),
+// then one copy, one sync.  Tiled with a CSR: the pack rides in csr_slots.
+inline double *RadialCall::pack(const AssignOut &a, int *nsum_out) {
+  const int nsum = (a.maccs || (dist && fs.nm)) ? fs.nm * (int)nb : 0;
+  const uint32_t ablocks = a.maccs ? a.ablocks : 0;
+  const PackLayout L(nq, (int)nb, nsum, dist);
+  const int ntot = L.ntot();
+  double *dpk = (double *)P.fpack.get(sizeof(double) * (size_t)(ntot + L.nloc));
+  const int nhead = (int)ceil_div(L.sums(), TPB);
+  const uint32_t npk = (uint32_t)(nhead + nsum);
+  uint64_t *pdone = nullptr;
+  double *hp = nullptr;
+  if (!dist) {
+    if (!P.pdone.p) {
+      P.pdone.get(sizeof(uint64_t));
+      PBX_HIP(hipMemsetAsync(P.pdone.p, 0, sizeof(uint64_t), st));
+      P.pack_done = 0;
+    }
+    pdone = (uint64_t *)P.pdone.p;
+    hp = (double *)P.mpin.get(sizeof(double) * (size_t)(ntot + 1));
+    hp[ntot] = __builtin_bit_cast(double, ~0ull);
+    dpk = (double *)P.mpin.dev;
+  }
+  const PackArgs pk{(const FusedCtl *)ctl, (const double *)de, nq, cnt, (int)nb,
+                    (const double *)a.maccs, (int64_t)ablocks, nsum, dpk, a.cnt_offs, nt, nhead,
+                    (const double *)a.maccs2, a.maccs2 ? (int64_t)g0 : 0, pdone,
+                    P.pack_done + npk, ntot,
+                    P.tsum.p ? (const unsigned long long *)prim::scan_watchdog(P.tsum) : nullptr,
+                    !dist ? (double *)P.pstage.get(sizeof(double) * (size_t)ntot) : nullptr};
+  auto csr = [&](int np) {
+    hipLaunchKernelGGL(csr_slots, dim3(nt), dim3(TPB), 0, st, (const uint32_t *)P.toff.p,
+                       (const uint64_t *)P.kw.p, (const uint16_t *)P.kpre.p,
+                       (const uint32_t *)P.swc.p, (const uint8_t *)a.bins8, (const uint32_t *)a.th,
+                       nt, (int32_t *)P.perm.get(sizeof(int32_t) * (size_t)n_sel),
+                       (uint32_t)nb + 1, pk, np);
+  };
+  if (a.csr_pack && npk <= nt) {  // the pack rides in csr_slots' first npk blocks
+    csr((int)npk);
+  } else {
+    if (a.csr_pack) csr(0);
+    hipLaunchKernelGGL(fused_pack, dim3(npk), dim3(TPB), 0, st, pk);
+  }
+  PBX_HIP(hipGetLastError());
+  if (!dist) {
+    P.pack_done += npk;
+    if (!wait_tag(st, hp + ntot, P.pack_done))
+      fail(PBX_ERR_RUNTIME, "the results pack of a radial profile call did not complete");
+  } else {  // this rank's counts kept after the global results
+    PBX_HIP(hipMemcpyAsync(dpk + ntot, dpk + L.counts(), sizeof(double) * nb,
+                           hipMemcpyDeviceToDevice, st));
+    comm_allreduce(comm, dpk + L.counts(), dpk + L.counts(), nb, 2, 0, st, lk);  // counts (u64)
+    comm_allreduce(comm, dpk + L.sums(), dpk + L.sums(), nsum, 0, 0, st, lk);    // sums
+    hp = (double *)P.pin.get(sizeof(double) * (size_t)(ntot + L.nloc));
+    PBX_HIP(hipMemcpyAsync(hp, dpk, sizeof(double) * (ntot + L.nloc), hipMemcpyDeviceToHost, st));
+    PBX_HIP(hipStreamSynchronize(st));
+  }
+  *nsum_out = nsum;
+  return hp;
+}
+
+// The multi-kernel path; returns the host results pack (radial_mono_run's
+// contract) after the call's one sync (dist: one more, in resolve).
+static double *radial_multi_run(RadialCall &C, const SelectReq &q, int *nsum) {
+  C.select(q);
+  C.level0();
+  C.resolve();
+  AssignOut a;
+  if (C.agath) a = C.assign_tiled();
+  else C.gather();
+  C.finish(a);
+  if (!C.agath && C.n_sel) a = C.lazy ? C.assign_lazy() : C.assign_eager();
+  return C.pack(a, nsum);
+}
+
+// ---- after the pack ------------------------------------------------------
+struct RadialOut {  // the entry points' outputs
+  int64_t *n_kept;
+  double *h_edges;
+  int64_t *n_edges, *h_counts, *n_valid;
+  double *h_moments;
+  int64_t *h_counts_local;  // dist (optional): this rank's counts
+};
+
+// a tiled call's counters and the speculation state for the next call
+static void note_tiled_call(Profile &P, const FusedCtl &c, const double *he, int nq, bool dist) {
+  ++P.n_tiled_calls;
+  if (c.hint) ++P.n_hinted;
+  if (c.spec & SPEC_HIT) ++P.n_spec_hit;
+  if (c.spec & SPEC_EDGE) ++P.n_edge_hit;
+  P.spec_next = !dist && (c.spec & SPEC_MATCH);
+  // edge speculation next: this call's digits matched and its edges are
+  // the previous call's, bit for bit
+  const bool same = (int64_t)P.last_edges.size() == nq &&
+                    std::memcmp(P.last_edges.data(), he, sizeof(double) * nq) == 0;
+  P.edge_next = P.spec_next && same;
+  P.last_edges.assign(he, he + nq);
+  // a hit stored no x (ensure_x rebuilds it on demand); a miss rebuilt it
+  P.x_missing = (c.spec & SPEC_NOX) && (c.spec & SPEC_HIT);
+  P.spec_dirty = false;  // fused_finish cleared the flag word and the edge counts
+}
+
+// The pack's error bits, the handle's state after the call, the copy-out
+// (plan.fs.nm == 0 with statistics: separate moment passes, one more sync).
+static void finish_call(RadialCall &C, const double *hp, const PackLayout &L, const StatReq &s,
+                        const StatPlan &plan, double *accs, const RadialOut &o) {
+  Profile &P = C.P;
+  hipStream_t st = C.st;
+  const bool dist = C.dist;
+  const int nq = L.nq;
+  const int64_t nb = L.nb;
+  const FusedCtl c = *(const FusedCtl *)hp;
+  const double *he = hp + L.edges();
+  if (c.err & 1) fail(PBX_ERR_RUNTIME, "selection look-back did not complete");
+  if (c.err & 4) {  // (the watchdog word is sticky: cleared as it is reported)
+    PBX_HIP(hipMemsetAsync(prim::scan_watchdog(P.tsum), 0, sizeof(uint64_t), st));
+    fail(PBX_ERR_RUNTIME, "a device scan of the profile step did not complete (look-back watchdog)");
+  }
+  if (C.tiled) note_tiled_call(P, c, he, nq, dist);
+  P.mm[0] = c.kmin;
+  P.mm[1] = c.kmax;
+  select_commit(P, c.n);
+  if (dist) P.mm_valid = false;  // the pack's key range is the global one
+  *o.n_kept = c.n;
+  if ((dist ? C.n_global : c.n) == 0) fail(PBX_ERR_VALUE, "Cannot create bins: input array is empty");
+  if ((c.err & 2) || c.m == 0) fail(PBX_ERR_VALUE, "index 0 is out of bounds for axis 0 with size 0");
+  std::memcpy(o.h_edges, he, sizeof(double) * nq);
+  int64_t sv = 0;  // this rank's particles in bins
+  if (c.m < 2) {
+    one_bin_redo(P, st, o.h_edges, C.build_csr, s, accs);
+    const void *counts = P.counts.p;
+    if (dist) {
+      PBX_HIP(hipMemcpyAsync(&sv, P.counts.p, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+      PBX_HIP(hipStreamSynchronize(st));
+      int64_t *gc = (int64_t *)P.dscal.get(sizeof(int64_t) * 4 + sizeof(FusedCtl));
+      PBX_HIP(hipMemcpyAsync(gc, P.counts.p, sizeof(int64_t), hipMemcpyDeviceToDevice, st));
+      comm_allreduce(C.comm, gc, gc, 1, 1, 0, st, C.lk);
+      comm_allreduce(C.comm, accs, accs, (int64_t)s.n * NMOM, 0, 0, st, C.lk);
+      counts = gc;
+    }
+    one_bin_out(st, s, accs, counts, o.h_counts, o.h_moments);
+    if (!dist) sv = o.h_counts[0];
+    else if (o.h_counts_local) o.h_counts_local[0] = sv;
+    *o.n_edges = 2;
+  } else {
+    P.nb = nb;
+    P.csr_ready = C.build_csr != 0;
+    std::memcpy(o.h_counts, hp + L.counts(), sizeof(int64_t) * nb);
+    const int64_t *hl = (const int64_t *)(dist ? hp + L.ntot() : hp + L.counts());
+    for (int64_t b = 0; b < nb; ++b) sv += hl[b];
+    if (dist && o.h_counts_local) std::memcpy(o.h_counts_local, hl, sizeof(int64_t) * nb);
+    if (plan.fs.nm) {
+      expand_sums(plan, s.n, nb, hp + L.sums(), o.h_moments);
+    } else if (s.n) {  // too many distinct sums to fuse: separate passes
+      const int64_t len = nb * NMOM;
+      stat_moments(P, st, s, accs, len);
+      if (dist) comm_allreduce(C.comm, accs, accs, (int64_t)s.n * len, 0, 0, st, C.lk);
+      PBX_HIP(hipMemcpyAsync(o.h_moments, accs, sizeof(double) * s.n * len, hipMemcpyDeviceToHost, st));
+      PBX_HIP(hipStreamSynchronize(st));
+    }
+    *o.n_edges = nq;
+  }
+  P.n_valid = sv;
+  *o.n_valid = sv;
+}
+
+
 static Profile &as_profile(void *h) {
   if (!h) fail(PBX_ERR_VALUE, "null profile handle");
   Profile *p = (Profile *)h;
   int dev = current_device().id;
   if (p->device != dev) fail(PBX_ERR_VALUE, "profile belongs to device %d", p->device);
   return *p;
+}
+
+// an entry point's body with the handle's profile, under its device's lock
+template <typename F>
+static int with_profile(void *handle, F &&body) {
+  return guard([&] {
+    Profile &P = as_profile(handle);
+    Device &d = current_device();
+    std::lock_guard<std::mutex> lk(d.mu);
+    body(P, d, d.stream);
+  });
 }
 
 }  // namespace prof
@@ -5678,7 +6338,7 @@ int pbx_profile_destroy(void *handle) {
     Buf *all[] = {&p->x, &p->w, &p->idx, &p->bins, &p->perm, &p->keys0, &p->keys1, &p->vtmp,
                   &p->hist, &p->tsum, &p->edges, &p->counts, &p->minmax, &p->slab, &p->acc,
                   &p->field, &p->weight, &p->ranks, &p->bounds, &p->msH, &p->msR, &p->msG,
-                  &p->msNg, &p->msM, &p->msRows, &p->msL0, &p->msL1, &p->msCnt, &p->csrh, &p->slabp, &p->selst, &p->accs,
+                  &p->msNg, &p->msM, &p->msRows, &p->msL0, &p->msL1, &p->csrh, &p->slabp, &p->selst, &p->accs,
                   &p->pk0, &p->pk1, &p->pv0, &p->pv1, &p->pbk, &p->pcdf, &p->poff, &p->pq, &p->pout,
                   &p->fctl, &p->fseg, &p->fgrp, &p->fslab, &p->fpack, &p->frec, &p->fblk,
                   &p->bins8, &p->kw, &p->toff, &p->mstage, &p->xc, &p->kpre, &p->shint, &p->shs, &p->srows,
@@ -5693,23 +6353,29 @@ int pbx_profile_destroy(void *handle) {
   });
 }
 
-int pbx_profile_level0_stats(void *handle, int64_t *out) {
+// the handle's counters, in the order of pbx.h's *_stats entries
+static int counters_out(void *handle, int64_t *out, std::initializer_list<int64_t Profile::*> which) {
   return guard([&] {
     Profile &P = as_profile(handle);
     if (!out) fail(PBX_ERR_VALUE, "null output");
-    out[0] = P.n_tiled_calls;
-    out[1] = P.n_hinted;
+    for (auto m : which) *out++ = P.*m;
   });
 }
 
+int pbx_profile_level0_stats(void *handle, int64_t *out) {
+  return counters_out(handle, out, {&Profile::n_tiled_calls, &Profile::n_hinted});
+}
+
 int pbx_profile_spec_stats(void *handle, int64_t *out) {
-  return guard([&] {
-    Profile &P = as_profile(handle);
-    if (!out) fail(PBX_ERR_VALUE, "null output");
-    out[0] = P.n_spec;
-    out[1] = P.n_spec_hit;
-    out[2] = P.n_edge_hit;
-  });
+  return counters_out(handle, out, {&Profile::n_spec, &Profile::n_spec_hit, &Profile::n_edge_hit});
+}
+
+int pbx_profile_mono_stats(void *handle, int64_t *out) {
+  return counters_out(handle, out, {&Profile::n_mono, &Profile::n_mono_hinted, &Profile::n_mono_edge});
+}
+
+int pbx_profile_path_stats(void *handle, int64_t *out) {
+  return counters_out(handle, out, {&Profile::n_mono, &Profile::n_mono_discard, &Profile::n_multi});
 }
 
 int pbx_profile_set_source_stable(void *handle, int stable) {
@@ -5739,32 +6405,9 @@ int pbx_profile_set_level0_hint(void *handle, int enabled) {
   });
 }
 
-int pbx_profile_mono_stats(void *handle, int64_t *out) {
-  return guard([&] {
-    Profile &P = as_profile(handle);
-    if (!out) fail(PBX_ERR_VALUE, "null output");
-    out[0] = P.n_mono;
-    out[1] = P.n_mono_hinted;
-    out[2] = P.n_mono_edge;
-  });
-}
-
-int pbx_profile_path_stats(void *handle, int64_t *out) {
-  return guard([&] {
-    Profile &P = as_profile(handle);
-    if (!out) fail(PBX_ERR_VALUE, "null output");
-    out[0] = P.n_mono;
-    out[1] = P.n_mono_discard;
-    out[2] = P.n_multi;
-  });
-}
-
 int pbx_profile_set_x(void *handle, const double *h_x, int64_t n) {
-  return guard([&] {
-    Profile &P = as_profile(handle);
+  return with_profile(handle, [&](Profile &P, Device &d, hipStream_t st) {
     check_n(n);
-    Device &d = current_device();
-    std::lock_guard<std::mutex> lk(d.mu);
     double *x = (double *)P.x.get(sizeof(double) * (size_t)(n ? n : 1));
     if (n) h2d_staged(d, x, h_x, sizeof(double) * n, d.stream);  // (through pinned chunks)
     P.n = n;
@@ -5792,18 +6435,14 @@ int pbx_profile_select_typed(void *handle, const void *pos, int pos_dtype, const
                              int mass_dtype, int64_t n, int on_device, int use_sphere,
                              const double *sphere, const int64_t *fam, int nfam, int ndim,
                              int64_t *n_kept) {
-  return guard([&] {
-    Profile &P = as_profile(handle);
+  return with_profile(handle, [&](Profile &P, Device &d, hipStream_t st) {
     if ((pos_dtype != PBX_F64 && pos_dtype != PBX_F32) ||
         (mass_dtype != PBX_F64 && mass_dtype != PBX_F32))
       fail(PBX_ERR_VALUE, "dtype must be PBX_F64 or PBX_F32");
-    Device &d = current_device();
-    std::lock_guard<std::mutex> lk(d.mu);
-    hipStream_t st = d.stream;
     ScopedTimer tm("pbx.profile.select");
-    const uint32_t nt = select_launch(P, st, pos, mass, n, on_device, use_sphere, sphere, fam,
-                                      nfam, ndim, false, pos_dtype == PBX_F32,
-                                      mass_dtype == PBX_F32);
+    const SelectReq q{pos, mass, n, on_device, use_sphere, sphere, fam, nfam, ndim,
+                      pos_dtype == PBX_F32, mass_dtype == PBX_F32};
+    const uint32_t nt = select_launch(P, st, q);
     int64_t kept = 0;
     if (nt) {
       uint64_t *stat = (uint64_t *)P.selst.p;
@@ -5827,11 +6466,7 @@ int pbx_profile_select_typed(void *handle, const void *pos, int pos_dtype, const
 }
 
 int pbx_profile_get_selection(void *handle, int64_t *h_idx, double *h_x, double *h_w) {
-  return guard([&] {
-    Profile &P = as_profile(handle);
-    Device &d = current_device();
-    std::lock_guard<std::mutex> lk(d.mu);
-    hipStream_t st = d.stream;
+  return with_profile(handle, [&](Profile &P, Device &d, hipStream_t st) {
     if (!P.has_idx) fail(PBX_ERR_VALUE, "profile has no selection");
     const int64_t n = P.n;
     if (n == 0) return;
@@ -5855,11 +6490,7 @@ int pbx_profile_get_selection(void *handle, int64_t *h_idx, double *h_x, double 
 
 // np.min / np.max of x (NaN propagates to both, like numpy)
 int pbx_profile_minmax(void *handle, double *mn, double *mx) {
-  return guard([&] {
-    Profile &P = as_profile(handle);
-    Device &d = current_device();
-    std::lock_guard<std::mutex> lk(d.mu);
-    hipStream_t st = d.stream;
+  return with_profile(handle, [&](Profile &P, Device &d, hipStream_t st) {
     if (P.n == 0) fail(PBX_ERR_VALUE, "zero-size array to reduction operation minimum which has no identity");
     uint64_t h[2];
     minmax_of(P, st, h);
@@ -5872,10 +6503,7 @@ int pbx_profile_minmax(void *handle, double *mn, double *mx) {
 
 // ---- distributed equaln: the radix select in stages ----
 int pbx_profile_key_range(void *handle, uint64_t *kmin, uint64_t *kmax) {
-  return guard([&] {
-    Profile &P = as_profile(handle);
-    Device &d = current_device();
-    std::lock_guard<std::mutex> lk(d.mu);
+  return with_profile(handle, [&](Profile &P, Device &d, hipStream_t st) {
     uint64_t h[2] = {~0ull, 0ull};
     if (P.n) minmax_of(P, d.stream, h);
     *kmin = h[0];
@@ -5895,29 +6523,20 @@ int pbx_profile_msel_begin(void *handle, int64_t nbins, int has_min, double bin_
 }
 
 int pbx_profile_msel_hist(void *handle, int level, uint32_t **d_hist, int64_t *count) {
-  return guard([&] {
-    Profile &P = as_profile(handle);
-    Device &d = current_device();
-    std::lock_guard<std::mutex> lk(d.mu);
+  return with_profile(handle, [&](Profile &P, Device &d, hipStream_t st) {
     *count = msel_hist(P, d.stream, level);
     *d_hist = (uint32_t *)P.msH.p;
   });
 }
 
 int pbx_profile_msel_resolve(void *handle, int level) {
-  return guard([&] {
-    Profile &P = as_profile(handle);
-    Device &d = current_device();
-    std::lock_guard<std::mutex> lk(d.mu);
+  return with_profile(handle, [&](Profile &P, Device &d, hipStream_t st) {
     msel_resolve_level(P, d.stream, level);
   });
 }
 
 int pbx_profile_msel_edges(void *handle, double *h_edges, int64_t *n_edges) {
-  return guard([&] {
-    Profile &P = as_profile(handle);
-    Device &d = current_device();
-    std::lock_guard<std::mutex> lk(d.mu);
+  return with_profile(handle, [&](Profile &P, Device &d, hipStream_t st) {
     msel_edges_out(P, d.stream, h_edges, n_edges);
   });
 }
@@ -5927,12 +6546,8 @@ int pbx_profile_msel_edges(void *handle, double *h_edges, int64_t *n_edges) {
 // for the degenerate < 2 case; 0 with status VALUE for empty input).
 int pbx_profile_edges_equaln(void *handle, int64_t nbins, int has_min, double bin_min,
                              int has_max, double bin_max, double *h_edges, int64_t *n_edges) {
-  return guard([&] {
-    Profile &P = as_profile(handle);
+  return with_profile(handle, [&](Profile &P, Device &d, hipStream_t st) {
     if (nbins < 1) fail(PBX_ERR_VALUE, "nbins must be >= 1");
-    Device &d = current_device();
-    std::lock_guard<std::mutex> lk(d.mu);
-    hipStream_t st = d.stream;
     ScopedTimer tm("pbx.profile.equaln");
     const int64_t n = P.n;
     if (n == 0) fail(PBX_ERR_VALUE, "Cannot create bins: input array is empty");
@@ -5953,7 +6568,7 @@ int pbx_profile_edges_equaln(void *handle, int64_t nbins, int has_min, double bi
     int hb = diff ? 63 - __builtin_clzll(diff) : -1;
     uint64_t *a = k0, *b = k1;
     for (int shift = 0; shift <= hb; shift += 8) {
-      radix_pass<uint64_t>(P, st, a, nullptr, VAL_NONE, n, shift, b, nullptr);
+      prim::radix_pass<uint64_t>(P.hist, P.tsum, st, a, nullptr, VAL_NONE, n, shift, b, nullptr);
       std::swap(a, b);
     }
     // clip window [lo, hi) of the sorted keys: sorted_x[sorted_x >= bin_min]
@@ -6001,12 +6616,8 @@ int pbx_profile_edges_equaln(void *handle, int64_t nbins, int has_min, double bi
 // the CSR and moments use.  counts: nb int64 (host).
 int pbx_profile_assign(void *handle, const double *h_edges, int64_t n_edges, int64_t *h_counts,
                        int64_t *n_valid) {
-  return guard([&] {
-    Profile &P = as_profile(handle);
+  return with_profile(handle, [&](Profile &P, Device &d, hipStream_t st) {
     if (n_edges < 2) fail(PBX_ERR_VALUE, "Explicit bin_edges must be a 1D array of length >= 2");
-    Device &d = current_device();
-    std::lock_guard<std::mutex> lk(d.mu);
-    hipStream_t st = d.stream;
     ScopedTimer tm("pbx.profile.assign");
     double *de = (double *)P.edges.get(sizeof(double) * (size_t)n_edges);
     PBX_HIP(hipMemcpyAsync(de, h_edges, sizeof(double) * n_edges, hipMemcpyHostToDevice, st));
@@ -6025,12 +6636,8 @@ int pbx_profile_assign(void *handle, const double *h_edges, int64_t n_edges, int
 // each bin = the reference's binind lists concatenated) and offsets (nb+1).
 // Either output may be NULL (then the CSR stays on the device only).
 int pbx_profile_csr(void *handle, int64_t *h_perm, int64_t *h_offsets) {
-  return guard([&] {
-    Profile &P = as_profile(handle);
+  return with_profile(handle, [&](Profile &P, Device &d, hipStream_t st) {
     if (P.nb < 0) fail(PBX_ERR_VALUE, "call pbx_profile_assign first");
-    Device &d = current_device();
-    std::lock_guard<std::mutex> lk(d.mu);
-    hipStream_t st = d.stream;
     ScopedTimer tm("pbx.profile.csr");
     const int64_t nb = P.nb;
     csr_device(P, st);
@@ -6066,12 +6673,8 @@ int pbx_profile_moments(void *handle, int f_src, const double *h_f, int w_src, c
 // and Σf·w (pynbodyext.profiles.proarray derives the set per statistic)
 int pbx_profile_moments_cols(void *handle, int f_src, const double *h_f, int w_src,
                              const double *h_w, uint32_t cols, double *h_out) {
-  return guard([&] {
-    Profile &P = as_profile(handle);
+  return with_profile(handle, [&](Profile &P, Device &d, hipStream_t st) {
     if (P.nb < 0) fail(PBX_ERR_VALUE, "call pbx_profile_assign first");
-    Device &d = current_device();
-    std::lock_guard<std::mutex> lk(d.mu);
-    hipStream_t st = d.stream;
     ScopedTimer tm("pbx.profile.moments");
     const int64_t len = P.nb * NMOM;
     double *acc = (double *)P.acc.get(sizeof(double) * (size_t)std::max<int64_t>(len, 1));
@@ -6090,26 +6693,12 @@ int pbx_profile_binned_equaln(void *handle, int64_t nbins, int has_min, double b
                               const int *f_src, const int *w_src, const uint32_t *cols,
                               double *h_edges, int64_t *n_edges, int64_t *h_counts,
                               int64_t *n_valid, double *h_moments) {
-  return guard([&] {
-    Profile &P = as_profile(handle);
-    if (nbins < 1) fail(PBX_ERR_VALUE, "nbins must be >= 1");
-    if (nbins + 1 > MS_MAXQ) fail(PBX_ERR_VALUE, "the fused path supports nbins <= %d", MS_MAXQ - 1);
-    if (n_stats < 0 || n_stats > 16) fail(PBX_ERR_VALUE, "at most 16 statistics");
-    for (int k = 0; k < n_stats; ++k)
-      if (f_src[k] < 0 || f_src[k] > 1 || w_src[k] < -1 || w_src[k] > 1)
-        fail(PBX_ERR_VALUE, "the fused path takes the profile's x / weights only");
-    Device &d = current_device();
-    std::lock_guard<std::mutex> lk(d.mu);
-    hipStream_t st = d.stream;
+  return with_profile(handle, [&](Profile &P, Device &d, hipStream_t st) {
+    const StatReq stats{n_stats, f_src, w_src, cols};
+    check_stat_args(nbins, stats);
     ScopedTimer tm("pbx.profile.binned_equaln");
     if (P.n == 0) fail(PBX_ERR_VALUE, "Cannot create bins: input array is empty");
-    uint64_t mm[2];
-    minmax_of(P, st, mm);
-    msel_begin(P, nbins, has_min, bin_min, has_max, bin_max, mm[0], mm[1]);
-    for (int l = 0; l < P.ms.L; ++l) {
-      msel_hist(P, st, l);
-      msel_resolve_level(P, st, l);
-    }
+    msel_levels(P, st, nbins, has_min, bin_min, has_max, bin_max);
     const int nq = P.ms.nq;
     double *de = (double *)P.edges.get(sizeof(double) * (size_t)nq);
     hipLaunchKernelGGL(msel_edges, dim3(ceil_div(nq, TPB)), dim3(TPB), 0, st,
@@ -6121,9 +6710,7 @@ int pbx_profile_binned_equaln(void *handle, int64_t nbins, int has_min, double b
     if (build_csr) csr_device(P, st);
     const int64_t len = nbins * NMOM;
     double *accs = (double *)P.accs.get(sizeof(double) * (size_t)std::max<int64_t>(1, n_stats * len));
-    for (int k = 0; k < n_stats; ++k)
-      moments_device(P, st, f_src[k], nullptr, P.field, w_src[k], nullptr, P.weight, cols[k],
-                     accs + k * len);
+    stat_moments(P, st, stats, accs, len);
     // async readbacks into pinned staging, one sync
     char *hp = (char *)P.pin.get(8 * (1 + nq + nbins + n_stats * len));
     int64_t *hm = (int64_t *)hp;
@@ -6142,19 +6729,8 @@ int pbx_profile_binned_equaln(void *handle, int64_t nbins, int has_min, double b
     if (n_stats) std::memcpy(h_moments, hmo, sizeof(double) * n_stats * len);
     if (m == 0) fail(PBX_ERR_VALUE, "index 0 is out of bounds for axis 0 with size 0");
     if (m < 2) {  // the reference's degenerate [s0, s0]: one bin, redo with 2 edges
-      h_edges[1] = h_edges[0];
-      double *de = (double *)P.edges.get(sizeof(double) * 2);
-      PBX_HIP(hipMemcpyAsync(de, h_edges, sizeof(double) * 2, hipMemcpyHostToDevice, st));
-      assign_device(P, st, de, 1);
-      if (build_csr) csr_device(P, st);
-      for (int k = 0; k < n_stats; ++k)
-        moments_device(P, st, f_src[k], nullptr, P.field, w_src[k], nullptr, P.weight, cols[k],
-                       accs + k * NMOM);
-      PBX_HIP(hipMemcpyAsync(h_counts, P.counts.p, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-      if (n_stats)
-        PBX_HIP(hipMemcpyAsync(h_moments, accs, sizeof(double) * n_stats * NMOM,
-                               hipMemcpyDeviceToHost, st));
-      PBX_HIP(hipStreamSynchronize(st));
+      one_bin_redo(P, st, h_edges, build_csr, stats, accs);
+      one_bin_out(st, stats, accs, P.counts.p, h_counts, h_moments);
       *n_edges = 2;
     } else {
       *n_edges = nq;
@@ -6176,14 +6752,10 @@ int pbx_profile_binned_equaln(void *handle, int64_t nbins, int has_min, double b
 int pbx_profile_percentiles(void *handle, int f_src, const double *h_f, int w_src,
                             const double *h_w, int absval, int nq, const double *q,
                             double *h_out) {
-  return guard([&] {
-    Profile &P = as_profile(handle);
+  return with_profile(handle, [&](Profile &P, Device &d, hipStream_t st) {
     if (P.nb < 0) fail(PBX_ERR_VALUE, "call pbx_profile_assign first");
     if (nq < 1 || nq > 4096) fail(PBX_ERR_VALUE, "1 to 4096 percentiles per call");
     if (f_src < 0 || f_src > 3 || w_src < -1 || w_src > 3) fail(PBX_ERR_VALUE, "bad source selector");
-    Device &d = current_device();
-    std::lock_guard<std::mutex> lk(d.mu);
-    hipStream_t st = d.stream;
     ScopedTimer tm("pbx.profile.percentiles");
     const int64_t nb = P.nb;
     double *out = (double *)P.pout.get(sizeof(double) * (size_t)std::max<int64_t>(1, nb * nq));
@@ -6211,589 +6783,28 @@ int pbx_profile_percentiles(void *handle, int f_src, const double *h_f, int w_sr
 // all-reduce of the zeroed segment array all-gathers them -> every rank
 // finishes the same edges; the packed counts and per-bin sums (sum).  The
 // ctl read-back after the resolve sizes the segment array on the host.
-static int radial_equaln_entry(void *comm, void *handle, const double *pos, const double *mass,
-                               int64_t n, int on_device, int use_sphere, const double *sphere,
-                               const int64_t *fam, int nfam, int ndim, int64_t nbins, int has_min,
-                               double bin_min, int has_max, double bin_max, int build_csr,
-                               int n_stats, const int *f_src, const int *w_src,
-                               const uint32_t *cols, int64_t *n_kept, double *h_edges,
-                               int64_t *n_edges, int64_t *h_counts, int64_t *n_valid,
-                               double *h_moments, int64_t *h_counts_local) {
+static int radial_equaln_entry(void *comm, void *handle, const SelectReq &q, int64_t nbins,
+                               int has_min, double bin_min, int has_max, double bin_max,
+                               int build_csr, const StatReq &stats, const RadialOut &out) {
   return guard([&] {
     Profile &P = as_profile(handle);
-    const bool dist = comm != nullptr;
-    const CommRanks cr = dist ? comm_ranks(comm) : CommRanks{1, 0};
-    if (nbins < 1) fail(PBX_ERR_VALUE, "nbins must be >= 1");
-    if (nbins + 1 > MS_MAXQ) fail(PBX_ERR_VALUE, "the fused path supports nbins <= %d", MS_MAXQ - 1);
-    if (n_stats < 0 || n_stats > 16) fail(PBX_ERR_VALUE, "at most 16 statistics");
-    for (int k = 0; k < n_stats; ++k)
-      if (f_src[k] < 0 || f_src[k] > 1 || w_src[k] < -1 || w_src[k] > 1)
-        fail(PBX_ERR_VALUE, "the fused path takes the profile's x / weights only");
+    const CommRanks cr = comm ? comm_ranks(comm) : CommRanks{1, 0};
+    check_stat_args(nbins, stats);
     Device &d = current_device();
     std::unique_lock<std::mutex> lk(d.mu);  // (released inside comm_allreduce's host wait)
     hipStream_t st = d.stream;
     ScopedTimer tm("pbx.profile.radial_equaln");
-    // bins < 256: the lazy selection + tile-walking assignment / CSR passes
-    const bool lazy = nbins < RADIX;
-    const int nq = (int)nbins + 1;
-    // the window of bins.py:734-737 as key bounds (msel_begin)
-    bool empty_bounds = false;
-    uint64_t ka = 0ull, kb = ~0ull;
-    if (has_min || has_max) {
-      kb = ~0ull - 1;
-      if (has_min) {
-        if (bin_min != bin_min) empty_bounds = true;
-        else ka = dkey(bin_min);
-      }
-      if (has_max) {
-        if (bin_max != bin_max) empty_bounds = true;
-        else kb = std::min<uint64_t>(kb, dkey(bin_max));
-      }
-    }
-    const int64_t nb = nbins;
-    // distinct monomials of the requested columns (x^a w^b |x|^c |w|^d);
-    // mono[k][c] = its slot, -1 = column not accumulated (0)
-    FusedStats fs{};
-    fs.nm = 0;
-    const int64_t len = nb * NMOM;
-    double *accs = (double *)P.accs.get(sizeof(double) * (size_t)std::max<int64_t>(1, n_stats * len));
-    std::vector<int> mono((size_t)n_stats * NMOM, -1);
-    std::vector<uint32_t> mkey;
-    bool fuse = n_stats > 0;
-    for (int k = 0; k < n_stats && fuse; ++k)
-      for (int c = 0; c < NMOM; ++c) {
-        if (!((cols[k] >> c) & 1u)) continue;
-        const bool wc = (c == 0 || c == 1 || c == 2 || c == 5);
-        if (wc && w_src[k] < 0) continue;  // unweighted: the weighted columns stay 0
-        uint32_t e[4] = {0, 0, 0, 0};       // powers of x, w, |x|, |w|
-        const int fp = (c == 2 || c == 4) ? 2 : (c == 0 ? 0 : 1);
-        const bool fa = (c == 5 || c == 6);
-        e[(fa ? 2 : 0) + f_src[k]] += fp;
-        if (wc) e[w_src[k]] += 1;
-        const uint32_t key = e[0] | e[1] << 4 | e[2] << 8 | e[3] << 12;
-        int slot = -1;
-        for (size_t j = 0; j < mkey.size(); ++j)
-          if (mkey[j] == key) slot = (int)j;
-        if (slot < 0) {
-          if (fs.nm == AS_MAXM || (int64_t)(fs.nm + 1) * nb > 2 * LDS_MOM_BINS * NMOM) {
-            fuse = false;
-            break;
-          }
-          slot = fs.nm++;
-          mkey.push_back(key);
-          fs.f[slot] = f_src[k];
-          fs.w[slot] = w_src[k];
-          fs.col[slot] = c;
-          fs.op[slot] = key == 0x010u ? MO_W : key == 0x001u ? MO_X : key == 0x011u ? MO_XW
-                      : key == 0x012u ? MO_XXW : key == 0x002u ? MO_XX : key == 0x020u ? MO_WW
-                      : MO_GEN;
-        }
-        mono[(size_t)k * NMOM + c] = slot;
-      }
-    if (!fuse) fs.nm = 0;
-    constexpr int NC = (int)(sizeof(FusedCtl) / sizeof(double));
-    static_assert(sizeof(FusedCtl) % sizeof(double) == 0, "FusedCtl packs as doubles");
+    const KeyWindow kw = key_window(has_min, bin_min, has_max, bin_max);
+    double *accs = (double *)P.accs.get(sizeof(double) *
+                                        (size_t)std::max<int64_t>(1, stats.n * nbins * NMOM));
+    const StatPlan plan = plan_stats(stats, nbins);
+    RadialCall C(P, st, comm, lk, cr, nbins, kw, plan.fs, build_csr);
     // small selections: the whole step as one persistent launch (radial_mono)
     double *hp = nullptr;
-    bool tiled_call = false;  // the multi-kernel path over a tiled selection
     int nsum = 0;
-    int64_t n_global = 0;  // dist: kept particles over all ranks
-    if (lazy && !dist)
-      hp = radial_mono_run(P, st, pos, mass, n, on_device, use_sphere, sphere, fam, nfam, ndim,
-                           nbins, ka, kb, empty_bounds, fs, &nsum);
-    if (!hp) {  // the multi-kernel path
-      ++P.n_multi;
-      // one rank, lazy: the level-0 histogram of a tiled selection is built by
-      // select_tiles with the previous tiled call's geometry (slot n_tiled & 1;
-      // fused_hist0 writes this call's into the other slot)
-      SelHint *hints = nullptr;
-      if (!dist && lazy && !P.hint_off) {
-        if (!P.shint.p) {
-          P.shint.get(2 * sizeof(SelHint));
-          PBX_HIP(hipMemsetAsync(P.shint.p, 0, 2 * sizeof(SelHint), st));
-        }
-        hints = (SelHint *)P.shint.p;
-      }
-      TileHist thist;
-      thist.hint = hints ? hints + (P.n_tiled & 1) : nullptr;
-      thist.cold = hints && P.n_tiled == 0;  // (no earlier tiled call left a geometry)
-      thist.ka = ka;
-      thist.kb = empty_bounds ? 0ull : kb;
-      // the speculative assignment: when the last tiled call's level-0 ranks
-      // matched the stored table (a repeated or similar call), select_tiles
-      // bins with it (checked by fused_resolve; a miss takes assign_tiles).
-      // It stores no x, which is then rebuilt from the positions on demand:
-      // only from positions the handle owns (staged host arrays) or that the
-      // caller declared stable
-      bool spec_ops = true;  // select_tiles' sums take the dedicated monomials only
-      for (int q = 0; q < fs.nm; ++q) spec_ops = spec_ops && fs.op[q] != MO_GEN;
-      if (hints && P.spec_next && P.stab.p && nb <= SPEC_MAXB && fs.nm * nb <= SPEC_MACC &&
-          spec_ops && (!on_device || P.src_stable)) {
-        thist.sa.tab = (const SpecTab *)P.stab.p;
-        thist.sa.fs = fs;
-        thist.sa.nb = (int)nb;
-        thist.sa.edge = P.edge_next ? 1 : 0;
-        if (thist.sa.edge && !P.slteq.p) {  // (zero before the first use; fused_resolve re-zeroes)
-          P.slteq.get(sizeof(uint32_t) * 2 * MS_MAXQ);
-          PBX_HIP(hipMemsetAsync(P.slteq.p, 0, sizeof(uint32_t) * 2 * MS_MAXQ, st));
-        }
-        thist.sa.lteq = (uint32_t *)P.slteq.p;
-        if (P.spec_dirty) {
-          if (P.sflag.p) PBX_HIP(hipMemsetAsync(P.sflag.p, 0, sizeof(uint32_t), st));
-          if (P.slteq.p) PBX_HIP(hipMemsetAsync(P.slteq.p, 0, sizeof(uint32_t) * 2 * MS_MAXQ, st));
-          P.spec_dirty = false;
-        }
-      }
-      const uint32_t nt = select_launch(P, st, pos, mass, n, on_device, use_sphere, sphere, fam,
-                                        nfam, ndim, lazy, 0, 0, /*tiled=*/true, &thist);
-      if (thist.spec) {
-        ++P.n_spec;
-        P.spec_dirty = true;  // (until the call's results arrive)
-      }
-      const bool hinted = hints && P.x_tiled;
-      tiled_call = P.x_tiled;
-      if (hinted) ++P.n_tiled;  // (the next tiled call reads the slot this one writes)
-      if (dist)  // global key range: every min / max slot pair (~min, max) max-reduced
-        comm_allreduce(comm, (uint64_t *)P.selst.p + nt + 1, (uint64_t *)P.selst.p + nt + 1,
-                       2 * MM_SLOTS, 2, 2, st, lk);
-      const int64_t n_sel = nt ? P.sel_span : 0;  // tiled particles (the families' span)
-      const bool tiled = P.x_tiled;  // x by tile (large inputs): tile offsets from fused_hist0
-      uint64_t *stat = (uint64_t *)P.selst.p;
-      FusedCtl *ctl = (FusedCtl *)P.fctl.get(sizeof(FusedCtl));
-      unsigned long long *cnt = (unsigned long long *)P.counts.get(sizeof(uint64_t) * (size_t)(nb + 1));
-      uint32_t *H = (uint32_t *)P.msH.get(sizeof(uint32_t) * MS0_DIG);
-      const int64_t *n_dev = &ctl->n;
-      const double *x = (const double *)P.x.p;
-      // level 0 (rows -> H), resolve + groups, per-block offsets, gather,
-      // per-group finish -> edges
-      const int g0 = fused_grid(n_sel);
-      uint32_t *rows = (uint32_t *)P.msRows.get(sizeof(uint32_t) * (size_t)g0 * MS0_DIG);
-      // tiled selections: assignment fused with the gather (assign_tiles),
-      // the deferred keys binned block by block by fix_deferred; the three
-      // per-block words [bcnt | rbase | rn] zeroed by fused_hist0
-      const bool agath = tiled && lazy && n_sel;
-      if (agath && g0 < 2) fail(PBX_ERR_RUNTIME, "tiled selection with one level-0 block");
-      // [bcnt | rbase | rn] per assignment workgroup (at_blocks: one per select block + 1)
-      const uint32_t nab = agath ? at_blocks(g0) : 0u;
-      uint32_t *bcnt = agath ? (uint32_t *)P.fblk.get(sizeof(uint32_t) * 3 * (size_t)nab) : nullptr;
-      const uint32_t *hflag = (const uint32_t *)(stat + nt + 1 + 2 * MM_SLOTS);
-      const FusedSetup fsu{(const uint64_t *)stat, nt, n_sel, ka, kb, (int)empty_bounds, (int)tiled,
-                           (uint32_t *)P.toff.p, bcnt, agath ? 3 * (int)nab : 0, (int)dist,
-                           (const uint64_t *)P.kw.p,
-                           hinted ? hints + ((P.n_tiled - 1) & 1) : nullptr, hflag,
-                           hinted ? hints + (P.n_tiled & 1) : nullptr, (const uint32_t *)P.sbt.p,
-                           thist.spec ? (const uint32_t *)thist.sa.flag : nullptr, thist.xs};
-      hipLaunchKernelGGL(fused_hist0, dim3(g0), dim3(MS0_TPB), 0, st, x, fsu, ctl, cnt, (int)nb,
-                         rows);
-      hipLaunchKernelGGL(msel_reduce0h, dim3(MS0_DIG / R0_DIG), dim3(MS0_TPB), 0, st,
-                         (const uint32_t *)rows, g0, hinted ? (const uint32_t *)P.srows.p : nullptr,
-                         hinted ? SH_K * (g0 - 1) * (int)P.sel_rsub : 0, (const int32_t *)&ctl->hint, H,
-                         stat + nt, 2 + 2 * MM_SLOTS);
-      PBX_HIP(hipGetLastError());
-      P.sel_tail_zero = stat + nt;  // (select_launch: no fill before the next tiled call)
-      int64_t *gsc = nullptr;  // dist: [global kept count][ctl copy]
-      uint32_t *lc_all = nullptr;
-      if (dist) {
-        gsc = (int64_t *)P.dscal.get(sizeof(int64_t) * 4 + sizeof(FusedCtl));
-        lc_all = (uint32_t *)P.dlc.get(sizeof(uint32_t) * (size_t)cr.nranks * MS_MAXQ);
-        PBX_HIP(hipMemsetAsync(lc_all, 0, sizeof(uint32_t) * (size_t)cr.nranks * MS_MAXQ, st));
-        // [global kept count, ranks whose look-back failed]
-        hipLaunchKernelGGL(dist_status, dim3(1), dim3(1), 0, st, (const FusedCtl *)ctl, gsc + 2);
-        comm_allreduce(comm, gsc + 2, gsc, 2, 1, 0, st, lk);
-        comm_allreduce(comm, H, H, MS0_DIG, 3, 0, st, lk);
-      }
-      MsRank *R = (MsRank *)P.msR.get(sizeof(MsRank) * (size_t)nq);
-      // [gdig | goff | gq | boff: a row per assignment workgroup (g0 or nab rows)]
-      uint32_t *gdig = (uint32_t *)P.fgrp.get(sizeof(uint32_t) * (3 + (size_t)std::max<uint32_t>(g0, nab)) *
-                                              (MS_MAXQ + 1));
-      uint32_t *goff = gdig + (MS_MAXQ + 1), *gq = goff + (MS_MAXQ + 1);
-      uint32_t *boff = gq + (MS_MAXQ + 1);
-      // the stored bin table (one rank, tiled assignment): allocated zeroed (invalid)
-      SpecTab *stab = nullptr;
-      if (agath && !dist) {
-        if (!P.stab.p) {
-          P.stab.get(sizeof(SpecTab));
-          PBX_HIP(hipMemsetAsync(P.stab.p, 0, sizeof(SpecTab), st));
-        }
-        stab = (SpecTab *)P.stab.p;
-      }
-      hipLaunchKernelGGL(fused_resolve, dim3(nq), dim3(FR_TPB), 0, st, (const uint32_t *)H, ctl,
-                         nbins, nq, R, gdig, goff, gq, (const uint32_t *)rows, g0, boff, bcnt,
-                         dist ? lc_all + (size_t)cr.rank * MS_MAXQ : nullptr,
-                         (const uint32_t *)P.srows.p, P.sel_rsub, (const SpecTab *)stab,
-                         thist.spec ? thist.sa.flag : nullptr, (int)nb,
-                         (thist.spec && thist.sa.edge) ? thist.sa.lteq : nullptr);
-      int64_t seg_total = 0;  // dist: keys in all ranks' group segments
-      if (dist) {
-        comm_allreduce(comm, lc_all, lc_all, (int64_t)cr.nranks * MS_MAXQ, 3, 0, st, lk);
-        hipLaunchKernelGGL(dist_rank_offsets, dim3(nq), dim3(TPB), 0, st, (const FusedCtl *)ctl,
-                           (const uint32_t *)lc_all, cr.rank, g0, boff);
-        PBX_HIP(hipGetLastError());
-        // the one extra read-back: the global segment length (and kept count)
-        FusedCtl *hc = (FusedCtl *)P.pin.get(sizeof(FusedCtl) + 16);
-        int64_t *hn = (int64_t *)(hc + 1);
-        PBX_HIP(hipMemcpyAsync(hc, ctl, sizeof(FusedCtl), hipMemcpyDeviceToHost, st));
-        PBX_HIP(hipMemcpyAsync(hn, gsc, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-        PBX_HIP(hipStreamSynchronize(st));
-        n_global = hn[0];
-        if (hn[1])  // (every rank sees the same sum: all fail here, no rank left in a collective)
-          fail(PBX_ERR_RUNTIME, "selection look-back did not complete (%lld of %d ranks)",
-               (long long)hn[1], cr.nranks);
-        seg_total = (hc->err & 2) ? 0 : hc->total;
-        if (n_global >= (int64_t)1 << 32)  // (every rank sees the same count: all fail here)
-          fail(PBX_ERR_VALUE, "distributed equaln over %lld particles: the u32 digit "
-               "histograms hold at most 2**32 - 1", (long long)n_global);
-      }
-      uint64_t *seg = (uint64_t *)P.fseg.get(
-          sizeof(uint64_t) * (size_t)std::max<int64_t>(1, std::max<int64_t>(n_sel, seg_total)));
-      if (seg_total) PBX_HIP(hipMemsetAsync(seg, 0, sizeof(uint64_t) * (size_t)seg_total, st));
-      double *de = (double *)P.edges.get(sizeof(double) * (size_t)nq);
-      uint32_t *bins = (uint32_t *)P.bins.get(sizeof(uint32_t) * (size_t)(n_sel ? n_sel : 1));
-      P.bins_in8 = agath;
-      double *maccs = nullptr, *maccs2 = nullptr;
-      P.csrh_ready = false;
-      uint32_t ablocks = 0;
-      const uint32_t *cnt_offs = nullptr;  // scanned CSR histogram the counts come from
-      bool csr_pack = false;  // tiled: csr_slots launched with the pack
-      uint32_t *th = nullptr;
-      uint8_t *bins8 = nullptr;
-      GatherOut go{};
-      SpecIO sio{};
-      if (agath) {
-        const int nr = (int)nb + 1;
-        const int64_t macc = (int64_t)fs.nm * nb;
-        th = (uint32_t *)P.csrh.get(sizeof(uint32_t) * (size_t)nt * nr);
-        bins8 = (uint8_t *)P.bins8.get((size_t)nt * TILE);  // by particle slot
-        // (nab: assign_tiles' workgroups = its slab rows)
-        double *slab = fs.nm ? (double *)P.fslab.get(sizeof(double) * (size_t)(nab + g0) * macc) : nullptr;
-        go = GatherOut{seg, (AgRec *)P.frec.get(sizeof(AgRec) * (size_t)n_sel), bcnt, bcnt + nab,
-                       bcnt + 2 * nab};
-        sio = SpecIO{stab, thist.spec ? thist.sa.rec : nullptr,
-                     thist.spec ? (const uint32_t *)thist.sa.rbase : nullptr,
-                     thist.spec ? (const uint32_t *)thist.sa.rn : nullptr,
-                     thist.spec ? (const double *)thist.sa.slab : nullptr};
-        if (thist.spec) {
-          // a speculating call: the hit's hand-over (assign_hit), and x from the
-          // positions for a miss whose selection stored none (xsrc_miss); each
-          // returns at once unless the call is its case
-          constexpr uint32_t xpb = 4;
-          hipLaunchKernelGGL(xsrc_miss, dim3(ceil_div(nt, xpb)), dim3(TPB), 0, st, (const FusedCtl *)ctl,
-                             thist.xs, nt, xpb);
-          if (fs.nm)
-            hipLaunchKernelGGL(assign_hit<true>, dim3(g0), dim3(MS0_TPB), 0, st, (const FusedCtl *)ctl,
-                               (const uint32_t *)gdig, (const uint32_t *)boff, (int)nb, fs, slab, go, sio);
-          else
-            hipLaunchKernelGGL(assign_hit<false>, dim3(g0), dim3(MS0_TPB), 0, st, (const FusedCtl *)ctl,
-                               (const uint32_t *)gdig, (const uint32_t *)boff, (int)nb, fs, slab, go, sio);
-        }
-        // the sums' form: {Σw, Σx·w} / {Σw} as dedicated adds, else any monomials
-        const int mm = (fs.nm == 2 && fs.op[0] == MO_W && fs.op[1] == MO_XW) ? 1
-                       : (fs.nm == 1 && fs.op[0] == MO_W) ? 2 : 0;
-        const size_t lds = sizeof(double) * (size_t)macc + sizeof(uint32_t) * (size_t)(nr | 1) * AT_TR;
-        auto at = [&](auto kern) {
-          hipLaunchKernelGGL(kern, dim3(nab), dim3(AT_BT), lds, st, x, (const uint64_t *)P.kw.p,
-                             P.sel_base, P.sel_span, nt, P.sel_mass, (const FusedCtl *)ctl, ka, kb,
-                             (const MsRank *)R, nq, (const uint32_t *)gdig, boff, (int)nb, bins8, th, fs,
-                             slab, go, stab, g0);
-        };
-        if (!fs.nm) at(assign_tiles<false, 0>);
-        else if (mm == 1) at(assign_tiles<true, 1>);
-        else if (mm == 2) at(assign_tiles<true, 2>);
-        else at(assign_tiles<true, 0>);
-        PBX_HIP(hipGetLastError());
-        ablocks = nab;
-        if (fs.nm) {
-          maccs = slab;
-          maccs2 = slab + (size_t)nab * macc;
-        }
-      } else {
-        hipLaunchKernelGGL(fused_gather, dim3(g0), dim3(MS0_TPB), 0, st, x, ka, kb,
-                           (const FusedCtl *)ctl, (const uint32_t *)gdig, (const uint32_t *)boff,
-                           seg, tiled ? (const uint64_t *)P.kw.p : nullptr, nt);
-      }
-      if (dist)  // every rank's group keys, each in its own slice: the all-gather
-        comm_allreduce(comm, seg, seg, seg_total, 2, 0, st, lk);
-      hipLaunchKernelGGL(fused_finish, dim3(nq), dim3(FR_TPB), 0, st, (const FusedCtl *)ctl,
-                         (const MsRank *)R, (const uint32_t *)gq, (const uint32_t *)goff,
-                         (const uint64_t *)seg, de, (const SpecTab *)stab, nq,
-                         thist.spec ? thist.sa.flag : nullptr,
-                         (thist.spec && thist.sa.edge) ? thist.sa.lteq : nullptr);
-      PBX_HIP(hipGetLastError());
-      // assignment (+ the statistics' distinct sums) with the device edges
-      if (agath) {
-        const uint32_t nr = (uint32_t)nb + 1;
-        const size_t lds = sizeof(double) * ((size_t)fs.nm * nb + nb + 1) + sizeof(uint32_t) * FD_LDSW;
-        auto fd = [&](auto kern) {
-          hipLaunchKernelGGL(kern, dim3(g0), dim3(MS0_TPB), lds, st, (const FusedCtl *)ctl,
-                             (const AgRec *)go.rec, (const uint32_t *)go.rbase,
-                             (const uint32_t *)go.rn, (const double *)de, (const uint32_t *)gq,
-                             (int)nb, bins8, th, nt, fs, maccs2, sio);
-        };
-        if (fs.nm) fd(fix_deferred<true>);
-        else fd(fix_deferred<false>);
-        PBX_HIP(hipGetLastError());
-        // (a row-wise scan — one block per bin row, its base from row totals
-        // summed by assign_gather / fix_deferred — took 15-16 us against this
-        // one-pass look-back scan's 11 us at 64M: dropped)
-        scan_u32(P, st, th, (int64_t)nt * nr);
-        cnt_offs = th;
-        // the CSR pass (csr_slots) is launched with the results pack below
-        // (its first blocks carry the pack)
-        csr_pack = build_csr;
-      } else if (n_sel && lazy) {
-        // tile-walking assignment over the lazy selection + its CSR pass
-        const int64_t macc = (int64_t)fs.nm * nb;
-        const bool ldse = (nb + 1) <= LDS_EDGES;
-        const size_t lds = sizeof(double) * (size_t)macc + (ldse ? sizeof(double) * (nb + 1) : 0);
-        uint32_t *th = (uint32_t *)P.csrh.get(sizeof(uint32_t) * (size_t)nt * RADIX);
-        const uint32_t tpbk = std::min<uint32_t>(AS_TILES, std::max<uint32_t>(1, nt / 1024));
-        ablocks = ceil_div(nt, tpbk);
-        double *slab = fs.nm ? (double *)P.fslab.get(sizeof(double) * (size_t)ablocks * macc) : nullptr;
-        const uint64_t *kwp = (const uint64_t *)P.kw.p;
-        const uint32_t *tof = (const uint32_t *)P.toff.p;
-        // few tiles: one tile per 1024-thread block, every wave a piece of it
-        const bool wide = tpbk == 1 && nt < 1024;
-        auto go = [&](auto kern, int bt) {
-          hipLaunchKernelGGL(kern, dim3(ablocks), dim3(bt), lds, st, x, kwp, tof, P.sel_base, nt,
-                             tpbk, P.sel_mass, (const double *)de, (int)nb, bins, th, fs, slab,
-                             tiled ? 1 : 0);
-        };
-        if (wide) {
-          if (fs.nm) {
-            if (ldse) go(assign_sel<true, true, 1024>, 1024);
-            else go(assign_sel<true, false, 1024>, 1024);
-          } else {
-            if (ldse) go(assign_sel<false, true, 1024>, 1024);
-            else go(assign_sel<false, false, 1024>, 1024);
-          }
-        } else if (fs.nm) {
-          if (ldse) go(assign_sel<true, true, TPB>, TPB);
-          else go(assign_sel<true, false, TPB>, TPB);
-        } else {
-          if (ldse) go(assign_sel<false, true, TPB>, TPB);
-          else go(assign_sel<false, false, TPB>, TPB);
-        }
-        PBX_HIP(hipGetLastError());
-        if (fs.nm) maccs = slab;
-        // the counts are row-start differences of the scanned [bin][tile] table
-        scan_u32(P, st, th, (int64_t)nt * RADIX);
-        cnt_offs = th;
-        if (build_csr) {
-          int32_t *perm = (int32_t *)P.perm.get(sizeof(int32_t) * (size_t)n_sel);
-          hipLaunchKernelGGL(csr_sel<uint32_t>, dim3(nt), dim3(TPB), 0, st, tof, n_dev, (const uint32_t *)bins,
-                             (const uint32_t *)th, nt, perm, (uint32_t)RADIX);
-          PBX_HIP(hipGetLastError());
-        }
-      } else if (n_sel) {
-        const int64_t macc = (int64_t)fs.nm * nb;
-        size_t lds = sizeof(double) * (size_t)macc +
-                     ((nb + 1) <= LDS_EDGES ? sizeof(double) * (nb + 1) : 0) +
-                     sizeof(uint32_t) * (nb + 1);
-        if (lds > 150 * 1024) fail(PBX_ERR_VALUE, "too many bins for the device histogram (%lld)", (long long)nb);
-        uint32_t *th = (nb < RADIX) ? (uint32_t *)P.csrh.get(sizeof(uint32_t) * (size_t)nt * RADIX)
-                                    : nullptr;
-        const uint32_t tpbk = std::min<uint32_t>(AS_TILES, std::max<uint32_t>(1, nt / 1024));
-        ablocks = ceil_div(nt, tpbk);
-        double *slab = fs.nm ? (double *)P.fslab.get(sizeof(double) * (size_t)ablocks * macc) : nullptr;
-        // with the CSR pass, the bin counts are differences of its scanned
-        // [bin][tile] histogram: no global count atomics in assign_bins
-        if (th && build_csr) cnt_offs = th;
-        unsigned long long *acnt = cnt_offs ? nullptr : cnt;
-        if (fs.nm)
-          launch_assign<true>(ablocks, lds, st, x, n_sel, (const double *)de, (int)nb, bins, acnt, th,
-                              nt, tpbk, n_dev, (const double *)P.w.p, fs, slab);
-        else
-          launch_assign<false>(ablocks, lds, st, x, n_sel, (const double *)de, (int)nb, bins, acnt, th,
-                               nt, tpbk, n_dev, nullptr, fs, nullptr);
-        PBX_HIP(hipGetLastError());
-        P.csrh_ready = th != nullptr;
-        if (fs.nm) maccs = slab;  // its rows are summed inside fused_pack
-        if (build_csr) {  // stable counting sort of the bin ids, device length
-          int bits = 0;
-          while (((int64_t)1 << bits) <= nb) ++bits;
-          uint32_t *ka2 = (uint32_t *)P.keys0.get(sizeof(uint32_t) * (size_t)n_sel);
-          uint32_t *kb2 = (uint32_t *)P.keys1.get(sizeof(uint32_t) * (size_t)n_sel);
-          int32_t *va = (int32_t *)P.perm.get(sizeof(int32_t) * (size_t)n_sel);
-          int32_t *vb = (int32_t *)P.vtmp.get(sizeof(int32_t) * (size_t)n_sel);
-          const uint32_t *kin = bins;
-          bool first = true;
-          for (int shift = 0; shift < bits; shift += 8) {
-            const bool last = shift + 8 >= bits;
-            if (first) {
-              prim::radix_pass<uint32_t>(P.csrh_ready ? P.csrh : P.hist, P.tsum, st, kin, nullptr,
-                                         VAL_IOTA, n_sel, shift, last ? nullptr : ka2, va, P.csrh_ready,
-                                         n_dev);
-              first = false;
-            } else {
-              prim::radix_pass<uint32_t>(P.hist, P.tsum, st, ka2, va, VAL_ARRAY, n_sel, shift,
-                                         last ? nullptr : kb2, vb, false, n_dev);
-              std::swap(ka2, kb2);
-              std::swap(va, vb);
-            }
-          }
-          P.csrh_ready = false;
-          if ((void *)va != P.perm.p)
-            PBX_HIP(hipMemcpyAsync(P.perm.p, va, sizeof(int32_t) * n_sel, hipMemcpyDeviceToDevice, st));
-        }
-      }
-      // the results packed into one block: mapped host memory + tag (one rank), or a device block, one copy, one sync (dist)
-      // (dist: every rank packs the fused sums' columns, zeros without
-      // particles, so the all-reduced regions have the same length)
-      nsum = (maccs || (dist && fs.nm)) ? fs.nm * (int)nb : 0;
-      if (!maccs) ablocks = 0;
-      const int ntot = NC + nq + (int)nb + nsum;
-      const int nloc = dist ? (int)nb : 0;  // dist: this rank's counts after the global ones
-      double *dpk = (double *)P.fpack.get(sizeof(double) * (size_t)(ntot + nloc));
-      const int nhead = (int)ceil_div(NC + nq + (int)nb, TPB);
-      const uint32_t npk = (uint32_t)(nhead + nsum);
-      // one rank: the pack lands in mapped host memory with a completion tag
-      // (no D2H copy, no stream sync); dist: all-reduced on the device, copied
-      const bool mapped = !dist;
-      uint64_t *pdone = nullptr;
-      if (mapped) {
-        if (!P.pdone.p) {
-          P.pdone.get(sizeof(uint64_t));
-          PBX_HIP(hipMemsetAsync(P.pdone.p, 0, sizeof(uint64_t), st));
-          P.pack_done = 0;
-        }
-        pdone = (uint64_t *)P.pdone.p;
-        hp = (double *)P.mpin.get(sizeof(double) * (size_t)(ntot + 1));
-        hp[ntot] = __builtin_bit_cast(double, ~0ull);
-        dpk = (double *)P.mpin.dev;
-      }
-      const PackArgs pk{(const FusedCtl *)ctl, (const double *)de, nq, cnt, (int)nb,
-                        (const double *)maccs, (int64_t)ablocks, nsum, dpk, cnt_offs, nt, nhead,
-                        (const double *)maccs2, maccs2 ? (int64_t)g0 : 0, pdone,
-                        P.pack_done + npk, ntot,
-                        P.tsum.p ? (const unsigned long long *)prim::scan_watchdog(P.tsum) : nullptr,
-                        mapped ? (double *)P.pstage.get(sizeof(double) * (size_t)ntot) : nullptr};
-      auto csr = [&](int np) {
-        hipLaunchKernelGGL(csr_slots, dim3(nt), dim3(TPB), 0, st, (const uint32_t *)P.toff.p,
-                           (const uint64_t *)P.kw.p, (const uint16_t *)P.kpre.p,
-                           (const uint32_t *)P.swc.p, (const uint8_t *)bins8, (const uint32_t *)th,
-                           nt, (int32_t *)P.perm.get(sizeof(int32_t) * (size_t)n_sel),
-                           (uint32_t)nb + 1, pk, np);
-      };
-      if (csr_pack && npk <= nt) {  // the pack rides in csr_slots' first npk blocks
-        csr((int)npk);
-      } else {
-        if (csr_pack) csr(0);
-        hipLaunchKernelGGL(fused_pack, dim3(npk), dim3(TPB), 0, st, pk);
-      }
-      PBX_HIP(hipGetLastError());
-      if (mapped) {
-        P.pack_done += npk;
-        if (!wait_tag(st, hp + ntot, P.pack_done))
-          fail(PBX_ERR_RUNTIME, "the results pack of a radial profile call did not complete");
-      } else {
-        if (dist) {
-          PBX_HIP(hipMemcpyAsync(dpk + ntot, dpk + NC + nq, sizeof(double) * nb,
-                                 hipMemcpyDeviceToDevice, st));
-          comm_allreduce(comm, dpk + NC + nq, dpk + NC + nq, nb, 2, 0, st, lk);   // counts (u64)
-          comm_allreduce(comm, dpk + NC + nq + nb, dpk + NC + nq + nb, nsum, 0, 0, st, lk);  // sums
-        }
-        hp = (double *)P.pin.get(sizeof(double) * (size_t)(ntot + nloc));
-        PBX_HIP(hipMemcpyAsync(hp, dpk, sizeof(double) * (ntot + nloc), hipMemcpyDeviceToHost, st));
-        PBX_HIP(hipStreamSynchronize(st));
-      }
-    }
-    const FusedCtl *hc = (const FusedCtl *)hp;
-    const double *he = hp + NC;
-    const int64_t *hcn = (const int64_t *)(he + nq);
-    const double *hmo = (const double *)(hcn + nb);
-    const FusedCtl c = *hc;
-    if (c.err & 1) fail(PBX_ERR_RUNTIME, "selection look-back did not complete");
-    if (c.err & 4) {  // (the watchdog word is sticky: cleared as it is reported)
-      PBX_HIP(hipMemsetAsync(prim::scan_watchdog(P.tsum), 0, sizeof(uint64_t), st));
-      fail(PBX_ERR_RUNTIME, "a device scan of the profile step did not complete (look-back watchdog)");
-    }
-    if (tiled_call) {
-      ++P.n_tiled_calls;
-      if (c.hint) ++P.n_hinted;
-      if (c.spec & SPEC_HIT) ++P.n_spec_hit;
-      if (c.spec & SPEC_EDGE) ++P.n_edge_hit;
-      P.spec_next = !dist && (c.spec & SPEC_MATCH);
-      // edge speculation next: this call's digits matched and its edges are
-      // the previous call's, bit for bit
-      const bool same = (int64_t)P.last_edges.size() == nq &&
-                        std::memcmp(P.last_edges.data(), he, sizeof(double) * nq) == 0;
-      P.edge_next = P.spec_next && same;
-      P.last_edges.assign(he, he + nq);
-      // a hit stored no x (ensure_x rebuilds it on demand); a miss rebuilt it
-      P.x_missing = (c.spec & SPEC_NOX) && (c.spec & SPEC_HIT);
-      P.spec_dirty = false;  // fused_finish cleared the flag word and the edge counts
-    }
-    P.mm[0] = c.kmin;
-    P.mm[1] = c.kmax;
-    select_commit(P, c.n);
-    if (dist) P.mm_valid = false;  // the pack's key range is the global one
-    *n_kept = c.n;
-    if ((dist ? n_global : c.n) == 0) fail(PBX_ERR_VALUE, "Cannot create bins: input array is empty");
-    const int64_t m = c.m;
-    int64_t sv_local = 0;  // dist: this rank's particles in bins
-    if ((c.err & 2) || m == 0) fail(PBX_ERR_VALUE, "index 0 is out of bounds for axis 0 with size 0");
-    std::memcpy(h_edges, he, sizeof(double) * nq);
-    if (m < 2) {  // the reference's degenerate [s0, s0]: one bin, stepwise
-      h_edges[1] = h_edges[0];
-      double *de = (double *)P.edges.get(sizeof(double) * 2);
-      PBX_HIP(hipMemcpyAsync(de, h_edges, sizeof(double) * 2, hipMemcpyHostToDevice, st));
-      assign_device(P, st, de, 1);
-      if (build_csr) csr_device(P, st);
-      for (int k = 0; k < n_stats; ++k)
-        moments_device(P, st, f_src[k], nullptr, P.field, w_src[k], nullptr, P.weight, cols[k],
-                       accs + k * NMOM);
-      if (dist) {
-        PBX_HIP(hipMemcpyAsync(&sv_local, P.counts.p, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-        PBX_HIP(hipStreamSynchronize(st));
-        int64_t *gc = (int64_t *)P.dscal.get(sizeof(int64_t) * 4 + sizeof(FusedCtl));
-        PBX_HIP(hipMemcpyAsync(gc, P.counts.p, sizeof(int64_t), hipMemcpyDeviceToDevice, st));
-        comm_allreduce(comm, gc, gc, 1, 1, 0, st, lk);
-        comm_allreduce(comm, accs, accs, (int64_t)n_stats * NMOM, 0, 0, st, lk);
-        PBX_HIP(hipMemcpyAsync(h_counts, gc, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-      } else {
-        PBX_HIP(hipMemcpyAsync(h_counts, P.counts.p, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-      }
-      if (n_stats)
-        PBX_HIP(hipMemcpyAsync(h_moments, accs, sizeof(double) * n_stats * NMOM,
-                               hipMemcpyDeviceToHost, st));
-      PBX_HIP(hipStreamSynchronize(st));
-      *n_edges = 2;
-    } else {
-      P.nb = nb;
-      P.csr_ready = build_csr != 0;
-      std::memcpy(h_counts, hcn, sizeof(int64_t) * nb);
-      if (dist) {  // this rank's counts follow the packed (global) results
-        const int64_t *hl = (const int64_t *)(hp + NC + nq + nb + nsum);
-        for (int64_t b2 = 0; b2 < nb; ++b2) sv_local += hl[b2];
-        if (h_counts_local) std::memcpy(h_counts_local, hl, sizeof(int64_t) * nb);
-      }
-      if (fs.nm) {  // expand the monomial sums into [stat][bin][column]
-        for (int k = 0; k < n_stats; ++k)
-          for (int64_t b2 = 0; b2 < nb; ++b2)
-            for (int c = 0; c < NMOM; ++c) {
-              const int slot = mono[(size_t)k * NMOM + c];
-              h_moments[(k * nb + b2) * NMOM + c] = slot < 0 ? 0.0 : hmo[slot * nb + b2];
-            }
-      } else if (n_stats) {  // too many distinct sums to fuse: separate passes
-        for (int k = 0; k < n_stats; ++k)
-          moments_device(P, st, f_src[k], nullptr, P.field, w_src[k], nullptr, P.weight, cols[k],
-                         accs + k * len);
-        if (dist) comm_allreduce(comm, accs, accs, (int64_t)n_stats * len, 0, 0, st, lk);
-        PBX_HIP(hipMemcpyAsync(h_moments, accs, sizeof(double) * n_stats * len,
-                               hipMemcpyDeviceToHost, st));
-        PBX_HIP(hipStreamSynchronize(st));
-      }
-      *n_edges = nq;
-    }
-    const int64_t nbo = *n_edges - 1;
-    int64_t sv = 0;
-    for (int64_t k = 0; k < nbo; ++k) sv += h_counts[k];
-    if (dist) {
-      sv = sv_local;
-      if (h_counts_local && nbo == 1 && m < 2) h_counts_local[0] = sv_local;
-    }
-    P.n_valid = sv;
-    *n_valid = sv;
+    if (C.lazy && !C.dist) hp = radial_mono_run(P, st, q, nbins, kw, plan.fs, &nsum);
+    if (!hp) hp = radial_multi_run(C, q, &nsum);
+    finish_call(C, hp, PackLayout(C.nq, (int)nbins, nsum, C.dist), stats, plan, accs, out);
   });
 }
 
@@ -6805,10 +6816,11 @@ int pbx_profile_radial_equaln(void *handle, const double *pos, const double *mas
                               const uint32_t *cols, int64_t *n_kept, double *h_edges,
                               int64_t *n_edges, int64_t *h_counts, int64_t *n_valid,
                               double *h_moments) {
-  return radial_equaln_entry(nullptr, handle, pos, mass, n, on_device, use_sphere, sphere, fam, nfam,
-                             ndim, nbins, has_min, bin_min, has_max, bin_max, build_csr, n_stats,
-                             f_src, w_src, cols, n_kept, h_edges, n_edges, h_counts, n_valid,
-                             h_moments, nullptr);
+  return radial_equaln_entry(nullptr, handle,
+                             SelectReq{pos, mass, n, on_device, use_sphere, sphere, fam, nfam, ndim},
+                             nbins, has_min, bin_min, has_max, bin_max, build_csr,
+                             StatReq{n_stats, f_src, w_src, cols},
+                             RadialOut{n_kept, h_edges, n_edges, h_counts, n_valid, h_moments, nullptr});
 }
 
 int pbx_profile_radial_equaln_comm(void *comm, void *handle, const double *pos, const double *mass,
@@ -6820,10 +6832,12 @@ int pbx_profile_radial_equaln_comm(void *comm, void *handle, const double *pos, 
                                    int64_t *n_edges, int64_t *h_counts, int64_t *h_counts_local,
                                    int64_t *n_valid, double *h_moments) {
   if (!comm) return guard([&] { fail(PBX_ERR_VALUE, "null communicator"); });
-  return radial_equaln_entry(comm, handle, pos, mass, n, on_device, use_sphere, sphere, fam, nfam,
-                             ndim, nbins, has_min, bin_min, has_max, bin_max, build_csr, n_stats,
-                             f_src, w_src, cols, n_kept, h_edges, n_edges, h_counts, n_valid,
-                             h_moments, h_counts_local);
+  return radial_equaln_entry(comm, handle,
+                             SelectReq{pos, mass, n, on_device, use_sphere, sphere, fam, nfam, ndim},
+                             nbins, has_min, bin_min, has_max, bin_max, build_csr,
+                             StatReq{n_stats, f_src, w_src, cols},
+                             RadialOut{n_kept, h_edges, n_edges, h_counts, n_valid, h_moments,
+                                       h_counts_local});
 }
 
 }  // extern "C"
