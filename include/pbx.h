@@ -166,9 +166,15 @@ int pbx_direct_sym_accumulate(const double *d_src, int64_t n, int64_t u0, int64_
                               double *d_acc4);
 int pbx_direct_sym_finish(const double *d_acc4, int64_t lo, int64_t hi, int want, double *d_pot,
                           double *d_acc);
+/* When all n particles carry the same mass (compared bitwise on the device,
+ * per accumulate call) the pair loop runs without the mass and multiplies
+ * by it once per flushed partial sum.  Counters of the calling thread's
+ * device: pair-kernel launches of the uniform-mass and of the general
+ * instantiation (either pointer may be NULL). */
+int pbx_direct_sym_path_stats(int64_t *uniform_launches, int64_t *general_launches);
 
 /* ------------------------------------------------------------------ */
-/* gravity: Barnes-Hut octree                                          */
+/* gravity: Barnes-Hut octree                                         */
 /* ------------------------------------------------------------------ */
 /* Replaces the PyO3 class `Octree` (crates/pynbodyext-rust/src/gravity.rs:
  * 114-445) over crates/gravity/src/tree.rs + multipole.rs.  The tree lives

@@ -12,6 +12,26 @@
 // v_rsq_f64 itself (1/r to ~5e-8 relative, measured), 18 FP64 instructions
 // per pair, results within ~1e-7 of the reference (contract: 1e-5).
 //
+// Uniform mass (UNI): when all n particles carry bitwise the same mass m —
+// masses=None, a dark-matter-only snapshot, synthetic.plummer — the pair
+// loop leaves the mass out: both sides accumulate w and w^3 d (the two
+// g = m q products go, the potential FMAs become adds: 19 / 16 FP64
+// instructions per pair; the mass is neither loaded nor rotated, 7 instead
+// of 8 DPP moves per slot step), and m multiplies each partial sum once
+// where it leaves the registers (source side per chunk, target side per
+// unit), so acc4 keeps its meaning and scale.  mass_probe decides per
+// accumulate call on the device (bit patterns of rec[i].w against rec[0].w,
+// i < n; 16 bytes read back, ~0.025 ms at 1M); pbx_direct_sym_path_stats
+// counts the launches of either kind.  Same box at 1M, fast mode: 318.1 ->
+// 283.3 ms, SQ_INSTS_VALU -10.6 % (profiles/uniform_mass/).  The pads have
+// no mass to be zero there: they weigh m like every particle, at distance
+// ~1e100 k (k = 1 .. 3071) from the particles and from each other.  Per pad
+// that adds w <= 2e-100 to a potential sum that is >= (n - 1) / diameter and
+// w^3 d <= 8e-200 to an acceleration sum: nothing, for any system whose
+// coordinates stay below ~1e80 (s2 <= 6e207 stays finite, and no result
+// depends on how the denormal w^3 is rounded).  The pads' own accumulators
+// are never read.
+//
 // Decomposition: particles padded to a multiple of 4 x 64 kT (pads: zero
 // mass, far away, distinct).  I-block = 64 kT targets of one wave (kT per
 // lane), J-chunk = 64 kS sources.  A workgroup (4 waves) owns a superblock
@@ -102,7 +122,10 @@ __device__ __forceinline__ double rot_dpp(double v) {
 // One J-chunk for one wave.  SYMM: both sides; else chunk DOFF of the
 // wave's own I-block (target side only, self pair masked at rotation 0:
 // source slot ks of that chunk is target kt = DOFF * kS + ks).
-template <int WANT, bool SYMM, bool RAW, int DOFF = 0>
+// UNI (every particle has the same mass m): the pair loop sums w and w^3 d
+// without the mass — sm / tm are not loaded, held or rotated — and the
+// kernel multiplies by m where the partial sums leave the registers.
+template <int WANT, bool SYMM, bool RAW, bool UNI, int DOFF = 0>
 __device__ __forceinline__ void chunk(const double4 *__restrict__ rec, int64_t jbase, int lane,
                                       const double (&tx)[kT], const double (&ty)[kT],
                                       const double (&tz)[kT], const double (&tm)[kT],
@@ -116,7 +139,7 @@ __device__ __forceinline__ void chunk(const double4 *__restrict__ rec, int64_t j
     sx[k] = r.x;
     sy[k] = r.y;
     sz[k] = r.z;
-    sm[k] = r.w;
+    sm[k] = UNI ? 0.0 : r.w;
     sp[k] = sa[k] = sb[k] = sc[k] = 0.0;
   }
   const int addr = ((lane + 1) & 63) << 2;  // rotate: take the next lane's sources
@@ -127,8 +150,9 @@ __device__ __forceinline__ void chunk(const double4 *__restrict__ rec, int64_t j
       for (int kt = 0; kt < kT; ++kt) {
         double dx = sx[ks] - tx[kt], dy = sy[ks] - ty[kt], dz = sz[ks] - tz[kt];
         double ms = sm[ks];
+        bool self = false;
         if (!SYMM && kt == DOFF * kS + ks) {
-          const bool self = (r == 0);
+          self = (r == 0);
           ms = self ? 0.0 : ms;
           dx = self ? 1.0 : dx;
         }
@@ -137,19 +161,20 @@ __device__ __forceinline__ void chunk(const double4 *__restrict__ rec, int64_t j
         const double y0 = __builtin_amdgcn_rsq(s2);
         // precise: one Newton step, w = 2/r (~1e-16); fast: w = v_rsq_f64 =
         // 1/r to ~5e-8 relative (3 FP64 instructions fewer per pair)
-        const double w = RAW ? y0 : y0 * __builtin_fma(-s2, y0 * y0, 3.0);
+        double w = RAW ? y0 : y0 * __builtin_fma(-s2, y0 * y0, 3.0);
+        if (UNI && !SYMM && kt == DOFF * kS + ks) w = self ? 0.0 : w;  // no mass to mask
         const double q = w * (w * w);  // w^3
-        if (WANT & PBX_WANT_POT) tp[kt] = __builtin_fma(ms, w, tp[kt]);
+        if (WANT & PBX_WANT_POT) tp[kt] = UNI ? tp[kt] + w : __builtin_fma(ms, w, tp[kt]);
         if (WANT & PBX_WANT_ACC) {
-          const double g = ms * q;
+          const double g = UNI ? q : ms * q;
           ta[kt] = __builtin_fma(g, dx, ta[kt]);
           tb[kt] = __builtin_fma(g, dy, tb[kt]);
           tc[kt] = __builtin_fma(g, dz, tc[kt]);
         }
         if (SYMM) {
-          if (WANT & PBX_WANT_POT) sp[ks] = __builtin_fma(tm[kt], w, sp[ks]);
+          if (WANT & PBX_WANT_POT) sp[ks] = UNI ? sp[ks] + w : __builtin_fma(tm[kt], w, sp[ks]);
           if (WANT & PBX_WANT_ACC) {
-            const double g = tm[kt] * q;
+            const double g = UNI ? q : tm[kt] * q;
             sa[ks] = __builtin_fma(-g, dx, sa[ks]);
             sb[ks] = __builtin_fma(-g, dy, sb[ks]);
             sc[ks] = __builtin_fma(-g, dz, sc[ks]);
@@ -164,7 +189,7 @@ __device__ __forceinline__ void chunk(const double4 *__restrict__ rec, int64_t j
       sx[ks] = rt(sx[ks], 0);
       sy[ks] = rt(sy[ks], 1);
       sz[ks] = rt(sz[ks], 2);
-      sm[ks] = rt(sm[ks], 3);
+      if (!UNI) sm[ks] = rt(sm[ks], 3);
       if (SYMM) {
         if (WANT & PBX_WANT_POT) sp[ks] = rt(sp[ks], 4);
         if (WANT & PBX_WANT_ACC) {
@@ -178,7 +203,7 @@ __device__ __forceinline__ void chunk(const double4 *__restrict__ rec, int64_t j
 }
 
 // chunk d of the wave's own I-block (d < kJPerI, a compile-time DOFF each)
-template <int WANT, bool RAW, int D>
+template <int WANT, bool RAW, bool UNI, int D>
 __device__ __forceinline__ void own_chunk(int d, const double4 *__restrict__ rec, int64_t jbase,
                                           int lane, const double (&tx)[kT], const double (&ty)[kT],
                                           const double (&tz)[kT], const double (&tm)[kT],
@@ -186,15 +211,16 @@ __device__ __forceinline__ void own_chunk(int d, const double4 *__restrict__ rec
                                           double (&tc)[kT], double (&sp)[kS], double (&sa)[kS],
                                           double (&sb)[kS], double (&sc)[kS]) {
   if (d == D)
-    chunk<WANT, false, RAW, D>(rec, jbase, lane, tx, ty, tz, tm, tp, ta, tb, tc, sp, sa, sb, sc);
+    chunk<WANT, false, RAW, UNI, D>(rec, jbase, lane, tx, ty, tz, tm, tp, ta, tb, tc, sp, sa, sb, sc);
   else if constexpr (D + 1 < kJPerI)
-    own_chunk<WANT, RAW, D + 1>(d, rec, jbase, lane, tx, ty, tz, tm, tp, ta, tb, tc, sp, sa, sb, sc);
+    own_chunk<WANT, RAW, UNI, D + 1>(d, rec, jbase, lane, tx, ty, tz, tm, tp, ta, tb, tc, sp, sa, sb,
+                                     sc);
 }
 
-template <int WANT, bool RAW>
+template <int WANT, bool RAW, bool UNI>
 __global__ void __launch_bounds__(kWaves * 64)
     sym_kernel(const double4 *__restrict__ rec, const Unit *__restrict__ units,
-               double *__restrict__ acc4) {
+               double *__restrict__ acc4, double m) {
   __shared__ double jl[kWaves][4][kChunk];  // source-side partials of one chunk, per wave
   const Unit u = units[blockIdx.x];
   const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -206,7 +232,7 @@ __global__ void __launch_bounds__(kWaves * 64)
     tx[k] = r.x;
     ty[k] = r.y;
     tz[k] = r.z;
-    tm[k] = r.w;
+    tm[k] = UNI ? 0.0 : r.w;
     tp[k] = ta[k] = tb[k] = tc[k] = 0.0;
   }
   const int64_t jdiag = iblk * kJPerI;  // this wave's first own chunk
@@ -215,11 +241,11 @@ __global__ void __launch_bounds__(kWaves * 64)
 #pragma unroll
     for (int k = 0; k < kS; ++k) sp[k] = sa[k] = sb[k] = sc[k] = 0.0;
     if (j >= jdiag + kJPerI)
-      chunk<WANT, true, RAW>(rec, (int64_t)j * kChunk, lane, tx, ty, tz, tm, tp, ta, tb, tc, sp, sa,
-                             sb, sc);
+      chunk<WANT, true, RAW, UNI>(rec, (int64_t)j * kChunk, lane, tx, ty, tz, tm, tp, ta, tb, tc, sp,
+                                  sa, sb, sc);
     else if (j >= jdiag)  // one of the wave's own chunks (target side, self pair masked)
-      own_chunk<WANT, RAW, 0>((int)(j - jdiag), rec, (int64_t)j * kChunk, lane, tx, ty, tz, tm, tp,
-                              ta, tb, tc, sp, sa, sb, sc);
+      own_chunk<WANT, RAW, UNI, 0>((int)(j - jdiag), rec, (int64_t)j * kChunk, lane, tx, ty, tz, tm,
+                                   tp, ta, tb, tc, sp, sa, sb, sc);
 #pragma unroll
     for (int k = 0; k < kS; ++k) {
       jl[w][0][k * 64 + lane] = sp[k];
@@ -236,7 +262,8 @@ __global__ void __launch_bounds__(kWaves * 64)
       for (int i = 0; i < kS; ++i) {
         const int idx = threadIdx.x + i * kWaves * 64;  // 0 .. 1023 = (source, quantity)
         const int s = idx >> 2, q = idx & 3;
-        const double v = jl[0][q][s] + jl[1][q][s] + jl[2][q][s] + jl[3][q][s];
+        double v = jl[0][q][s] + jl[1][q][s] + jl[2][q][s] + jl[3][q][s];
+        if (UNI) v *= m;
         if (v != 0.0) atomicAdd(dst + idx, v);
       }
     }
@@ -245,21 +272,40 @@ __global__ void __launch_bounds__(kWaves * 64)
 #pragma unroll
   for (int k = 0; k < kT; ++k) {
     double *dst = acc4 + (iblk * kBlk + k * 64 + lane) * 4;
-    if (WANT & PBX_WANT_POT) atomicAdd(dst + 0, tp[k]);
+    if (WANT & PBX_WANT_POT) atomicAdd(dst + 0, UNI ? m * tp[k] : tp[k]);
     if (WANT & PBX_WANT_ACC) {
-      atomicAdd(dst + 1, ta[k]);
-      atomicAdd(dst + 2, tb[k]);
-      atomicAdd(dst + 3, tc[k]);
+      atomicAdd(dst + 1, UNI ? m * ta[k] : ta[k]);
+      atomicAdd(dst + 2, UNI ? m * tb[k] : tb[k]);
+      atomicAdd(dst + 3, UNI ? m * tc[k] : tc[k]);
     }
   }
 }
 
-// records of n particles + pads up to npad (zero mass, far apart)
+// records of n particles + pads up to npad (zero mass, far apart; the
+// uniform-mass kernel never reads a mass: there a pad weighs m like the rest,
+// and only its distance keeps it out of the sums — see the header)
 __global__ void pad_records(double4 *__restrict__ rec, int64_t n, int64_t npad) {
   int64_t i = n + (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= npad) return;
-  const double far = 1e30 * (double)(i - n + 1);
+  const double far = 1e100 * (double)(i - n + 1);
   rec[i] = make_double4(far, -far, 2.0 * far, 0.0);
+}
+
+// Do the n particles (pads excluded) all carry the mass of particle 0?
+// Compared as bit patterns, so NaN and +-0 need no special case.  `out` is
+// zeroed before the launch; every thread that finds another mass stores 1.
+struct MassProbe {
+  double m;          // mass of particle 0
+  uint32_t differs;  // != 0: some particle has another mass
+  uint32_t pad;
+};
+__global__ void mass_probe(const double4 *__restrict__ rec, int64_t n,
+                           MassProbe *__restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const double m0 = rec[0].w;
+  if (i == 0) out->m = m0;
+  if (i < n && __builtin_bit_cast(uint64_t, rec[i].w) != __builtin_bit_cast(uint64_t, m0))
+    out->differs = 1u;
 }
 
 // undo the scaled accumulation: particles [lo, hi) -> outputs
@@ -303,6 +349,35 @@ static std::vector<sym::Unit> sym_units(int64_t npad) {
 
 int64_t sym_unit_count(int64_t n) { return (int64_t)sym_units(sym_padded(n)).size(); }
 
+// mass_probe over rec[0, n) and its 16-byte read-back (one stream sync; one
+// pass over the records: 32 MB at 1M).  GRAVITY_TIMING prints its stream time.
+static sym::MassProbe sym_probe_mass(Device &d, const double4 *rec, int64_t n) {
+  hipStream_t st = d.stream;
+  sym::MassProbe *dp = (sym::MassProbe *)d.slot(kSlotSymProbe).ensure(sizeof(sym::MassProbe));
+  sym::MassProbe h{};
+  const bool timed = timing_enabled();
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  if (timed) {
+    PBX_HIP(hipEventCreate(&e0));
+    PBX_HIP(hipEventCreate(&e1));
+    PBX_HIP(hipEventRecord(e0, st));
+  }
+  PBX_HIP(hipMemsetAsync(dp, 0, sizeof(sym::MassProbe), st));
+  hipLaunchKernelGGL(sym::mass_probe, dim3(ceil_div(n, 256)), dim3(256), 0, st, rec, n, dp);
+  PBX_HIP(hipGetLastError());
+  PBX_HIP(hipMemcpyAsync(&h, dp, sizeof(sym::MassProbe), hipMemcpyDeviceToHost, st));
+  if (timed) PBX_HIP(hipEventRecord(e1, st));
+  PBX_HIP(hipStreamSynchronize(st));
+  if (timed) {
+    float ms = 0.f;
+    PBX_HIP(hipEventElapsedTime(&ms, e0, e1));
+    std::fprintf(stderr, "[pynbodyext-timing] direct_sym mass probe (n=%lld): %.4f ms\n",
+                 (long long)n, (double)ms);
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+  }
+  return h;
+}
 
 
 // Units [u0, u1) of the (padded) record array into acc4 (npad x 4, caller
@@ -326,21 +401,36 @@ void sym_accumulate(Device &d, double4 *rec, int64_t n, int64_t u0, int64_t u1, 
   sym::Unit *du = (sym::Unit *)unit_buf.ensure(sizeof(sym::Unit) * mine.size());
   PBX_HIP(hipMemcpyAsync(du, mine.data(), sizeof(sym::Unit) * mine.size(), hipMemcpyHostToDevice,
                          st));
+  // one mass for all n particles?  (decided on the whole record array, so
+  // every rank of a sharded solve takes the same path; acc4 has the same
+  // scale on either)
+  const sym::MassProbe probe = sym_probe_mass(d, rec, n);
+  const bool uni = probe.differs == 0;
+  const double m = probe.m;
   const dim3 grid((unsigned)mine.size()), block(sym::kWaves * 64);
-  auto launch = [&](auto raw) {
-    constexpr bool R = decltype(raw)::value;
+  auto launch = [&](auto raw, auto uniform) {
+    constexpr bool R = decltype(raw)::value, U = decltype(uniform)::value;
     if (want == PBX_WANT_POT)
-      hipLaunchKernelGGL((sym::sym_kernel<PBX_WANT_POT, R>), grid, block, 0, st, rec, du, acc4);
+      hipLaunchKernelGGL((sym::sym_kernel<PBX_WANT_POT, R, U>), grid, block, 0, st, rec, du, acc4,
+                         m);
     else if (want == PBX_WANT_ACC)
-      hipLaunchKernelGGL((sym::sym_kernel<PBX_WANT_ACC, R>), grid, block, 0, st, rec, du, acc4);
+      hipLaunchKernelGGL((sym::sym_kernel<PBX_WANT_ACC, R, U>), grid, block, 0, st, rec, du, acc4,
+                         m);
     else
-      hipLaunchKernelGGL((sym::sym_kernel<PBX_WANT_POT | PBX_WANT_ACC, R>), grid, block, 0, st,
-                         rec, du, acc4);
+      hipLaunchKernelGGL((sym::sym_kernel<PBX_WANT_POT | PBX_WANT_ACC, R, U>), grid, block, 0, st,
+                         rec, du, acc4, m);
+  };
+  auto launch_raw = [&](auto raw) {
+    if (uni)
+      launch(raw, std::true_type{});
+    else
+      launch(raw, std::false_type{});
   };
   if (precise_mode())
-    launch(std::false_type{});
+    launch_raw(std::false_type{});
   else
-    launch(std::true_type{});
+    launch_raw(std::true_type{});
+  ++(uni ? d.sym_uniform_launches : d.sym_general_launches);
   PBX_HIP(hipGetLastError());
   // the unit table must outlive the launch before the host buffer goes away
   PBX_HIP(hipStreamSynchronize(st));
@@ -384,6 +474,15 @@ int pbx_direct_sym_accumulate(const double *d_src, int64_t n, int64_t u0, int64_
     double4 *rec = (double4 *)d.slot(kSlotSymRec).ensure(sizeof(double4) * npad);
     PBX_HIP(hipMemcpyAsync(rec, d_src, sizeof(double4) * n, hipMemcpyDeviceToDevice, d.stream));
     sym_accumulate(d, rec, n, u0, u1, want, d_acc4, d.slot(kSlotSymUnits));
+  });
+}
+
+int pbx_direct_sym_path_stats(int64_t *uniform_launches, int64_t *general_launches) {
+  return guard([&] {
+    Device &d = current_device();
+    std::lock_guard<std::mutex> lk(d.mu);
+    if (uniform_launches) *uniform_launches = d.sym_uniform_launches;
+    if (general_launches) *general_launches = d.sym_general_launches;
   });
 }
 

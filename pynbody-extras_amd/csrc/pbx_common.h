@@ -85,6 +85,9 @@ struct Device {
   std::vector<void *> ring;
   std::vector<hipEvent_t> ring_ev;
   std::vector<bool> ring_used;
+  // direct_sym.hip path counters (pbx_direct_sym_path_stats): sym_kernel
+  // launches of the uniform-mass and of the general instantiation
+  int64_t sym_uniform_launches = 0, sym_general_launches = 0;
 };
 
 // Workspace slot ids (one namespace for every module).
@@ -110,6 +113,7 @@ enum Slot {
   kSlotSymRec,
   kSlotSymAcc,
   kSlotSymUnits,
+  kSlotSymProbe,
   kSlotCount
 };
 
