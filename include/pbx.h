@@ -347,7 +347,8 @@ int pbx_profile_csr(void *handle, int64_t *h_perm, int64_t *h_offsets);
  * f_src / w_src: 0 = x, 1 = selection weights, 2 = host array (h_f / h_w,
  * n doubles in selection order), 3 = device array indexed by ORIGINAL
  * particle (gathered through the selection, e.g. a tree potential left in
- * HBM by pbx_octree_compute); w_src = -1: unweighted */
+ * HBM by pbx_octree_compute), PBX_SRC_KIN + code = a kinematic field (f_src
+ * only, see below); w_src = -1: unweighted */
 int pbx_profile_moments(void *handle, int f_src, const double *h_f, int w_src,
                         const double *h_w, double *h_out);
 /* the same for the columns whose bit is set in cols (bit k = column k of
@@ -355,6 +356,57 @@ int pbx_profile_moments(void *handle, int f_src, const double *h_f, int w_src,
  * (proarray.py:632-860 — Sum: Σf; weighted Mean: Σw, Σf·w; ...) */
 int pbx_profile_moments_cols(void *handle, int f_src, const double *h_f, int w_src,
                              const double *h_w, uint32_t cols, double *h_out);
+/* Kinematic fields of the kept particles, computed on the device from the
+ * ORIGINAL particles' positions and velocities — pynbody's derived arrays
+ * behind prof["vr"] (proarray.py:55-56, 179-187) and the profile's beta,
+ * without a per-field column on the host.  In float64, no FMA contraction,
+ * correctly rounded / and sqrt, in this order:
+ *   rxy2 = x*x + y*y;  r2 = rxy2 + z*z;  rxy = sqrt(rxy2);  r = sqrt(r2);
+ *   s = x*vx + y*vy;
+ *   vr = (s + z*vz) / r;            vrxy = s / rxy;
+ *   vphi = (x*vy - y*vx) / rxy;     vtheta = (z*vrxy - rxy*vz) / r;
+ *   v2 = (vx*vx + vy*vy) + vz*vz;   vt = sqrt(v2 - vr*vr)
+ * (0/0 on the z axis and at the origin is NaN, as numpy gives).  A field is
+ * named by its code, and PBX_SRC_KIN + code is a source selector (f_src) of
+ * pbx_profile_moments, pbx_profile_moments_cols and pbx_profile_percentiles:
+ * the field is then computed into the handle's stage buffer in selection
+ * order and consumed like any other source. */
+#define PBX_KIN_VR 0
+#define PBX_KIN_VTHETA 1
+#define PBX_KIN_VPHI 2
+#define PBX_KIN_VRXY 3
+#define PBX_KIN_V2 4
+#define PBX_KIN_VT 5
+#define PBX_SRC_KIN 16
+/* Register pos / vel, n x 3 doubles each, n = the length of the arrays the
+ * handle's selection was made from (after pbx_profile_set_x: the handle's
+ * own length, particle i = element i); another n is a PBX_ERR_VALUE.  Host
+ * arrays (on_device = 0) are staged into the handle, only the index span the
+ * selection covers, and may be released after the call; pos holds the
+ * positions the selection was made from (a handle that kept its staged copy
+ * of them reads that instead of staging pos again).  Device arrays
+ * (on_device = 1) are borrowed: they must stay allocated and unchanged until
+ * the next selection on this handle or until the registration is cleared.
+ * pos = vel = NULL clears it; every new selection (and pbx_profile_set_x)
+ * clears it too.  A kinematic source without a registration is a
+ * PBX_ERR_VALUE. */
+int pbx_profile_set_kinematics(void *handle, const double *pos, const double *vel, int64_t n,
+                               int on_device);
+/* field `code` of the kept particles in selection order into h_out (the
+ * selection's length, host) */
+int pbx_profile_kinematic_field(void *handle, int code, double *h_out);
+/* The fused pass: h_out[n_fields][nb][7] = the seven sums of
+ * pbx_profile_moments_cols for every field codes[k] under its column mask
+ * cols[k] (columns not requested are 0), from ONE read of the selection and
+ * the positions / velocities (64 B per kept particle) instead of a written
+ * and re-read column per field.  1 <= n_fields <= 6; w_src / h_w as
+ * pbx_profile_moments_cols (-1: unweighted, Σw and the weighted columns are
+ * then 0).  The per-bin accumulators live in LDS, one slot per requested
+ * (field, column) pair plus one shared Σw; when nb x slots exceeds the LDS
+ * footprint of the generic sums the call runs them field by field instead
+ * (same results to rounding). */
+int pbx_profile_kinematic_moments(void *handle, int n_fields, const int *codes, int w_src,
+                                  const double *h_w, const uint32_t *cols, double *h_out);
 /* One equaln radial-profile pass after pbx_profile_select with a single host
  * round trip (bins.py:720-746 edges, :346-395 assignment, the CSR when
  * build_csr, and per-bin sums of n_stats <= 16 requests (f_src / w_src in

@@ -4429,6 +4429,125 @@ __global__ void widen_perm(const int32_t *__restrict__ p, int64_t n, int64_t *__
   if (t < n) out[t] = p[t];
 }
 
+// -------------------------------------------------------- kinematic fields
+// Derived velocity fields of the kept particles from the ORIGINAL (N,3)
+// positions and velocities (pbx_profile_set_kinematics), gathered through
+// the selection's original indices: no per-field column on the host.  Field
+// codes: 0 vr, 1 vtheta, 2 vphi, 3 vrxy, 4 v2, 5 vt (pynbody's derived
+// arrays; vtheta in its algebraic form).  The expressions are evaluated in
+// the order pynbodyext.simcore states them, without FMA contraction, `/` and
+// sqrt correctly rounded, so a field equals numpy's bit for bit (0/0 on the
+// z axis and the origin is NaN, as there).
+constexpr int KIN_NF = 6;
+constexpr int KIN_IPT = 4;  // elements per lane per tile (16 loaded words each)
+constexpr int KIN_TILE = TPB * KIN_IPT;
+
+// f[c] for the codes c in `need` (and what they are made from); the rest 0
+__device__ __forceinline__ void kin_fields(const double p[3], const double v[3], uint32_t need,
+                                           double f[KIN_NF]) {
+#pragma clang fp contract(off)
+  const double x = p[0], y = p[1], z = p[2], vx = v[0], vy = v[1], vz = v[2];
+  const double rxy2 = x * x + y * y, r2 = rxy2 + z * z;
+  const double rxy = __builtin_sqrt(rxy2), r = __builtin_sqrt(r2);
+  const double s = x * vx + y * vy;
+  double vr = 0.0, vrxy = 0.0, v2 = 0.0;
+  if (need & (1u | 32u)) vr = (s + z * vz) / r;
+  if (need & (2u | 8u)) vrxy = s / rxy;
+  if (need & (16u | 32u)) v2 = (vx * vx + vy * vy) + vz * vz;
+  f[0] = vr;
+  f[1] = (need & 2u) ? (z * vrxy - rxy * vz) / r : 0.0;
+  f[2] = (need & 4u) ? (x * vy - y * vx) / rxy : 0.0;
+  f[3] = vrxy;
+  f[4] = v2;
+  f[5] = (need & 32u) ? __builtin_sqrt(v2 - vr * vr) : 0.0;
+}
+
+// (code is uniform: scalar compares)
+__device__ __forceinline__ double kin_pick(const double f[KIN_NF], int code) {
+  return code == 0 ? f[0] : code == 1 ? f[1] : code == 2 ? f[2] : code == 3 ? f[3]
+       : code == 4 ? f[4] : f[5];
+}
+
+// one field in selection order (idx NULL: identity, a set_x handle)
+__global__ void __launch_bounds__(TPB)
+    kin_field_kernel(const int32_t *__restrict__ idx, const double *__restrict__ pos,
+                     const double *__restrict__ vel, int64_t n, int code,
+                     double *__restrict__ out) {
+  const int64_t t = (int64_t)blockIdx.x * TPB + threadIdx.x;
+  if (t >= n) return;
+  const int64_t i = idx ? (int64_t)idx[t] : t;
+  const double p[3] = {pos[3 * i], pos[3 * i + 1], pos[3 * i + 2]};
+  const double v[3] = {vel[3 * i], vel[3 * i + 1], vel[3 * i + 2]};
+  double f[KIN_NF];
+  kin_fields(p, v, 1u << code, f);
+  out[t] = kin_pick(f, code);
+}
+
+// The fused pass: per-bin sums of several fields at once (moments_kernel's
+// sibling).  Accumulators are packed: acc[bin * nslots + slot], a slot only
+// for a requested (field, column) pair and one shared Σw slot, all in LDS
+// (the host falls back to one moments_kernel per field beyond its footprint).
+struct KinPlan {
+  int nf, nslots;
+  uint32_t need;               // bit c: field code c is evaluated
+  int8_t code[KIN_NF];
+  int8_t wslot;                // the shared Σw slot (-1: not accumulated)
+  int8_t slot[KIN_NF][NMOM];   // columns 1..6 of field k (-1: not accumulated)
+};
+
+__global__ void __launch_bounds__(TPB)
+    kin_moments_kernel(const uint32_t *__restrict__ bins, const int32_t *__restrict__ idx,
+                       const double *__restrict__ wt, const double *__restrict__ pos,
+                       const double *__restrict__ vel, int64_t n, int nb, KinPlan plan,
+                       double *__restrict__ slab) {
+  extern __shared__ double acc_lds[];
+  const int len = nb * plan.nslots;
+  for (int k = threadIdx.x; k < len; k += TPB) acc_lds[k] = 0.0;
+  __syncthreads();
+  for (int64_t base = (int64_t)blockIdx.x * KIN_TILE; base < n;
+       base += (int64_t)gridDim.x * KIN_TILE) {
+    uint32_t bv[KIN_IPT];  // the tile's loads first, then the LDS accumulation
+    double wv[KIN_IPT], p[KIN_IPT][3], v[KIN_IPT][3];
+#pragma unroll
+    for (int k = 0; k < KIN_IPT; ++k) {
+      const int64_t t = base + k * TPB + threadIdx.x;
+      const bool ok = t < n;
+      bv[k] = ok ? bins[t] : (uint32_t)nb;
+      const int64_t i = !ok ? 0 : idx ? (int64_t)idx[t] : t;
+      wv[k] = (wt && ok) ? wt[t] : 1.0;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        p[k][c] = ok ? pos[3 * i + c] : 1.0;
+        v[k][c] = ok ? vel[3 * i + c] : 0.0;
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < KIN_IPT; ++k) {
+      if (bv[k] >= (uint32_t)nb) continue;
+      double f[KIN_NF];
+      kin_fields(p[k], v[k], plan.need, f);
+      const double ww = wv[k];
+      double *a = acc_lds + (int)bv[k] * plan.nslots;
+      if (plan.wslot >= 0) atomicAdd(&a[plan.wslot], ww);
+#pragma unroll
+      for (int j = 0; j < KIN_NF; ++j) {
+        if (j >= plan.nf) break;
+        const double val = kin_pick(f, plan.code[j]), ab = __builtin_fabs(val);
+        const int8_t *s = plan.slot[j];
+        if (s[1] >= 0) atomicAdd(&a[s[1]], val * ww);
+        if (s[2] >= 0) atomicAdd(&a[s[2]], (val * val) * ww);
+        if (s[3] >= 0) atomicAdd(&a[s[3]], val);
+        if (s[4] >= 0) atomicAdd(&a[s[4]], val * val);
+        if (s[5] >= 0) atomicAdd(&a[s[5]], ab * ww);
+        if (s[6] >= 0) atomicAdd(&a[s[6]], ab);
+      }
+    }
+  }
+  __syncthreads();
+  double *dst = slab + (int64_t)blockIdx.x * len;
+  for (int k = threadIdx.x; k < len; k += TPB) dst[k] = acc_lds[k];
+}
+
 // ---------------------------------------------- per-bin order statistics
 // Percentile / Median / Abs_pXX (proarray.py:689-722): per bin, argsort the
 // field, cumsum the weights in that order (or linspace(0, 1, m) without
@@ -4717,6 +4836,13 @@ struct Profile {
   // select_tiles (the hinted geometry held: no re-read of x)
   int64_t n_tiled_calls = 0, n_hinted = 0;
   bool hint_off = false;  // pbx_profile_set_level0_hint(handle, 0): every tiled call re-reads x
+  // kinematic fields (pbx_profile_set_kinematics): the original particles'
+  // positions / velocities (src_n x 3; the caller's device arrays or the
+  // staged copies below), cleared by every new selection / set_x
+  int64_t src_n = 0;  // length of the arrays the selection was made from
+  const double *kin_pos = nullptr, *kin_vel = nullptr;
+  Buf kpos, kvel;
+  bool posst_sel = false;  // posst holds this selection's positions (a lazy selection of host arrays)
 };
 
 static void ensure_x(Profile &P, hipStream_t st);
@@ -5076,6 +5202,10 @@ static SelPrep select_prep(Profile &P, hipStream_t st, const SelectReq &q, bool 
   const size_t ms = mass_f32 ? sizeof(float) : sizeof(double);
   const void *pos = q.pos, *mass = q.mass, *d_pos = pos, *d_mass = mass;
   P.x_missing = false;
+  // a new selection: the registered kinematics go with the old one
+  P.src_n = n;
+  P.kin_pos = P.kin_vel = nullptr;
+  P.posst_sel = lazy && !q.on_device && n;
   if (!q.on_device && n) {
     // Only the families' span [lo, hi) is read: only it crosses PCIe, at its
     // own offset in an n-sized buffer (the kernels index particles
@@ -5315,8 +5445,34 @@ static void select_commit(Profile &P, int64_t kept) {
   P.nb = -1;
 }
 
+// ---- kinematic fields (pbx_profile_set_kinematics) ----------------------
+static void check_kin(const Profile &P) {
+  if (!P.kin_pos || !P.kin_vel)
+    fail(PBX_ERR_VALUE, "no kinematics registered for this selection (pbx_profile_set_kinematics)");
+}
+
+// the selection's original indices (NULL: identity, a set_x handle)
+static const int32_t *kin_idx(Profile &P, hipStream_t st) {
+  if (!P.has_idx) return nullptr;
+  ensure_idx(P, st);
+  return (const int32_t *)P.idx.p;
+}
+
+// field `code` of the kept particles, in selection order, into out (device)
+static void kin_field_device(Profile &P, hipStream_t st, int code, double *out) {
+  check_kin(P);
+  if (code < 0 || code >= KIN_NF) fail(PBX_ERR_VALUE, "bad kinematic field code %d", code);
+  const int64_t n = P.n;
+  if (!n) return;
+  const int32_t *idx = kin_idx(P, st);
+  hipLaunchKernelGGL(kin_field_kernel, dim3(ceil_div(n, TPB)), dim3(TPB), 0, st, idx, P.kin_pos,
+                     P.kin_vel, n, code, out);
+  PBX_HIP(hipGetLastError());
+}
+
 // device pointer of a per-element source: 0 = x, 1 = selection weights,
-// 2 = host array of n doubles (staged), 3 = device array per ORIGINAL particle
+// 2 = host array of n doubles (staged), 3 = device array per ORIGINAL particle,
+// PBX_SRC_KIN + code = a kinematic field (computed into the stage buffer)
 static const double *resolve_src(Profile &P, hipStream_t st, int which, const double *hp,
                                  Buf &stage) {
   const int64_t n = P.n;
@@ -5343,6 +5499,12 @@ static const double *resolve_src(Profile &P, hipStream_t st, int which, const do
     if (n)
       hipLaunchKernelGGL(gather_by_idx, dim3(ceil_div(n, TPB)), dim3(TPB), 0, st, hp,
                          (const int32_t *)P.idx.p, n, dp);
+    return dp;
+  }
+  if (which >= PBX_SRC_KIN && which < PBX_SRC_KIN + KIN_NF) {
+    check_kin(P);
+    double *dp = (double *)stage.get(sizeof(double) * (size_t)(n ? n : 1));
+    kin_field_device(P, st, which - PBX_SRC_KIN, dp);
     return dp;
   }
   fail(PBX_ERR_VALUE, "bad source selector %d", which);
@@ -6345,7 +6507,7 @@ int pbx_profile_destroy(void *handle) {
                   &p->swc, &p->sbt, &p->mono, &p->bar,
                   &p->mono_trace, &p->dscal, &p->dlc, &p->pdone, &p->pstage, &p->mH,
                   &p->mhint, &p->stab, &p->srec, &p->sspec, &p->sslab, &p->sflag, &p->posst,
-                  &p->slteq, &p->mpedges, &p->meue};
+                  &p->slteq, &p->mpedges, &p->meue, &p->kpos, &p->kvel};
     for (Buf *b : all) b->release();
     p->pin.release();
     p->mpin.release();
@@ -6411,6 +6573,9 @@ int pbx_profile_set_x(void *handle, const double *h_x, int64_t n) {
     double *x = (double *)P.x.get(sizeof(double) * (size_t)(n ? n : 1));
     if (n) h2d_staged(d, x, h_x, sizeof(double) * n, d.stream);  // (through pinned chunks)
     P.n = n;
+    P.src_n = n;
+    P.kin_pos = P.kin_vel = nullptr;
+    P.posst_sel = false;
     P.has_w = false;
     P.has_idx = false;
     P.lazy = false;
@@ -6684,6 +6849,128 @@ int pbx_profile_moments_cols(void *handle, int f_src, const double *h_f, int w_s
   });
 }
 
+// Register the ORIGINAL particles' positions and velocities (n x 3 doubles,
+// n = the length of the arrays the selection was made from; a set_x handle:
+// its own length) for the kinematic fields.  Host arrays are staged into the
+// handle, only the span the selection covers; device arrays are borrowed.
+// A NULL pair clears the registration; so does every new selection.
+int pbx_profile_set_kinematics(void *handle, const double *pos, const double *vel, int64_t n,
+                               int on_device) {
+  return with_profile(handle, [&](Profile &P, Device &d, hipStream_t st) {
+    if (!pos && !vel) {
+      P.kin_pos = P.kin_vel = nullptr;
+      return;
+    }
+    if (!pos || !vel) fail(PBX_ERR_VALUE, "positions and velocities are registered together");
+    if (n != P.src_n)
+      fail(PBX_ERR_VALUE, "kinematics of %lld particles, but the selection was made from %lld",
+           (long long)n, (long long)P.src_n);
+    if (on_device) {
+      P.kin_pos = pos;
+      P.kin_vel = vel;
+      return;
+    }
+    // (n-sized buffers: the kernels index particles absolutely)
+    const int64_t lo = P.has_idx ? P.sel_base : 0, span = P.has_idx ? P.sel_span : n;
+    const size_t row = sizeof(double) * 3;
+    auto stage = [&](Buf &b, const double *src) {
+      char *dp = (char *)b.get(row * (size_t)std::max<int64_t>(n, 1));
+      if (span) h2d_staged(d, dp + row * (size_t)lo, (const char *)src + row * (size_t)lo,
+                           row * (size_t)span, st);
+      return (const double *)dp;
+    };
+    // a lazy selection of host arrays kept its staged positions
+    P.kin_pos = (P.posst_sel && P.posst.p) ? (const double *)P.posst.p : stage(P.kpos, pos);
+    P.kin_vel = stage(P.kvel, vel);
+  });
+}
+
+// Field `code` of the kept particles, in selection order, to the host
+// (P.n doubles): the per-particle read behind sub["vr"].
+int pbx_profile_kinematic_field(void *handle, int code, double *h_out) {
+  return with_profile(handle, [&](Profile &P, Device &d, hipStream_t st) {
+    const int64_t n = P.n;
+    double *dp = (double *)P.field.get(sizeof(double) * (size_t)std::max<int64_t>(n, 1));
+    kin_field_device(P, st, code, dp);
+    if (n) d2h_staged(d, h_out, dp, sizeof(double) * n, st);
+    PBX_HIP(hipStreamSynchronize(st));
+  });
+}
+
+// The fused pass: h_out[n_fields][nb][7], the sums of pbx_profile_moments_cols
+// for every field k under its column mask cols[k], from one read of the
+// selection, positions and velocities (kin_moments_kernel).  Beyond the LDS
+// footprint of the packed accumulators: one generic pass per field.
+int pbx_profile_kinematic_moments(void *handle, int n_fields, const int *codes, int w_src,
+                                  const double *h_w, const uint32_t *cols, double *h_out) {
+  return with_profile(handle, [&](Profile &P, Device &d, hipStream_t st) {
+    if (P.nb < 0) fail(PBX_ERR_VALUE, "call pbx_profile_assign first");
+    if (n_fields < 1 || n_fields > KIN_NF) fail(PBX_ERR_VALUE, "1 to %d kinematic fields per call", KIN_NF);
+    if (!codes || !cols || !h_out) fail(PBX_ERR_VALUE, "null argument");
+    check_kin(P);
+    ScopedTimer tm("pbx.profile.kinematic_moments");
+    const int64_t n = P.n, nb = P.nb, len = nb * NMOM;
+    const bool weighted = w_src >= 0;
+    KinPlan plan{};
+    plan.nf = n_fields;
+    plan.wslot = -1;
+    for (int k = 0; k < n_fields; ++k) {
+      if (codes[k] < 0 || codes[k] >= KIN_NF) fail(PBX_ERR_VALUE, "bad kinematic field code %d", codes[k]);
+      plan.code[k] = (int8_t)codes[k];
+      plan.need |= 1u << codes[k];
+      // (unweighted: the weighted columns stay 0, as in moments_kernel)
+      const uint32_t c = cols[k] & (weighted ? 0x7fu : (8u | 16u | 64u));
+      for (int j = 0; j < NMOM; ++j) plan.slot[k][j] = -1;
+      for (int j = 1; j < NMOM; ++j)
+        if (c & (1u << j)) plan.slot[k][j] = (int8_t)plan.nslots++;
+      if (c & 1u) {
+        if (plan.wslot < 0) plan.wslot = (int8_t)plan.nslots++;
+        plan.slot[k][0] = plan.wslot;
+      }
+    }
+    std::memset(h_out, 0, sizeof(double) * (size_t)(n_fields * len));
+    if (!n || nb <= 0 || !plan.nslots) return;
+    const int64_t plen = nb * plan.nslots;
+    if (plen > (int64_t)LDS_MOM_BINS * NMOM) {  // the generic path, field by field
+      double *acc = (double *)P.acc.get(sizeof(double) * (size_t)len);
+      for (int k = 0; k < n_fields; ++k) {
+        moments_device(P, st, PBX_SRC_KIN + codes[k], nullptr, P.field, w_src, h_w, P.weight,
+                       cols[k] & 0x7fu, acc);
+        PBX_HIP(hipMemcpyAsync(h_out + (size_t)k * len, acc, sizeof(double) * len,
+                               hipMemcpyDeviceToHost, st));
+        PBX_HIP(hipStreamSynchronize(st));
+      }
+      return;
+    }
+    const double *w = weighted ? resolve_src(P, st, w_src, h_w, P.weight) : nullptr;
+    const int32_t *idx = kin_idx(P, st);
+    ensure_bins32(P, st);
+    // <= 1024 blocks stride over the tiles: one slab row each
+    const uint32_t nt = std::min<uint32_t>(ceil_div(n, KIN_TILE), 1024u);
+    double *slab = (double *)P.slab.get(sizeof(double) * (size_t)nt * plen);
+    double *acc = (double *)P.acc.get(sizeof(double) * (size_t)plen);
+    double *part = (double *)P.slabp.get(sizeof(double) * (size_t)SLAB_G * plen);
+    hipLaunchKernelGGL(kin_moments_kernel, dim3(nt), dim3(TPB), sizeof(double) * (size_t)plen, st,
+                       (const uint32_t *)P.bins.p, idx, w, P.kin_pos, P.kin_vel, n, (int)nb, plan,
+                       slab);
+    PBX_HIP(hipGetLastError());
+    hipLaunchKernelGGL(reduce_slab_part, dim3(ceil_div(plen, TPB), SLAB_G), dim3(TPB), 0, st, slab,
+                       (int64_t)nt, plen, part);
+    hipLaunchKernelGGL(reduce_slab_final, dim3(ceil_div(plen, TPB)), dim3(TPB), 0, st, part, plen,
+                       acc);
+    PBX_HIP(hipGetLastError());
+    double *hp = (double *)P.pin.get(sizeof(double) * (size_t)plen);
+    PBX_HIP(hipMemcpyAsync(hp, acc, sizeof(double) * plen, hipMemcpyDeviceToHost, st));
+    PBX_HIP(hipStreamSynchronize(st));
+    for (int k = 0; k < n_fields; ++k)
+      for (int j = 0; j < NMOM; ++j) {
+        const int s = plan.slot[k][j];
+        if (s < 0) continue;
+        for (int64_t b = 0; b < nb; ++b) h_out[((size_t)k * nb + b) * NMOM + j] = hp[b * plan.nslots + s];
+      }
+  });
+}
+
 // One radial-profile pass after pbx_profile_select, with a single host
 // round trip: equaln edges (radix select, kept on the device), assignment
 // with those edges, the CSR (optional) and the per-bin sums of n_stats
@@ -6755,7 +7042,9 @@ int pbx_profile_percentiles(void *handle, int f_src, const double *h_f, int w_sr
   return with_profile(handle, [&](Profile &P, Device &d, hipStream_t st) {
     if (P.nb < 0) fail(PBX_ERR_VALUE, "call pbx_profile_assign first");
     if (nq < 1 || nq > 4096) fail(PBX_ERR_VALUE, "1 to 4096 percentiles per call");
-    if (f_src < 0 || f_src > 3 || w_src < -1 || w_src > 3) fail(PBX_ERR_VALUE, "bad source selector");
+    const bool f_kin = f_src >= PBX_SRC_KIN && f_src < PBX_SRC_KIN + KIN_NF;
+    if (((f_src < 0 || f_src > 3) && !f_kin) || w_src < -1 || w_src > 3)
+      fail(PBX_ERR_VALUE, "bad source selector");
     ScopedTimer tm("pbx.profile.percentiles");
     const int64_t nb = P.nb;
     double *out = (double *)P.pout.get(sizeof(double) * (size_t)std::max<int64_t>(1, nb * nq));

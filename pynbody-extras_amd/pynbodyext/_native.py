@@ -31,6 +31,10 @@ KERNEL_SPLINE = 1
 WANT_POT = 1
 WANT_ACC = 2
 
+# kinematic field codes and their source-selector base (pbx.h PBX_KIN_* / PBX_SRC_KIN)
+KINEMATIC_FIELDS = ("vr", "vtheta", "vphi", "vrxy", "v2", "vt")
+SRC_KIN = 16
+
 _LIB_NAME = "libpbx.so"
 _lib: ctypes.CDLL | None = None
 
@@ -136,6 +140,10 @@ _SIGNATURES: dict[str, tuple] = {
     "pbx_profile_moments": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, _dp]),
     "pbx_profile_moments_cols": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_uint32,
                                          _dp]),
+    "pbx_profile_set_kinematics": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int]),
+    "pbx_profile_kinematic_field": (c_int, [c_void_p, c_int, _dp]),
+    "pbx_profile_kinematic_moments": (c_int, [c_void_p, c_int, POINTER(c_int), c_int, c_void_p,
+                                              POINTER(c_uint32), _dp]),
     "pbx_profile_percentiles": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int,
                                         c_void_p, c_void_p]),
     "pbx_profile_radial_equaln": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int,

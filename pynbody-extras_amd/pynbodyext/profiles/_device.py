@@ -18,6 +18,7 @@ NMOM = 7  # Σw, Σf·w, Σf²·w, Σf, Σf², Σ|f|·w, Σ|f|
 ALL_COLS = (1 << NMOM) - 1
 SRC_X, SRC_W, SRC_HOST, SRC_DEVICE, SRC_NONE = 0, 1, 2, 3, -1
 PBX_F64, PBX_F32 = 0, 1  # element types of pbx_profile_select_typed
+KINEMATIC_FIELDS = nat.KINEMATIC_FIELDS  # by field code (pbx.h PBX_KIN_*)
 
 _i64p = ctypes.POINTER(c_int64)
 
@@ -48,6 +49,7 @@ class DeviceBins:
         self.n_valid = 0
         self.has_selection = False
         self._csr = None
+        self._kin = None  # registered (pos, vel) of the kinematic fields, kept alive
 
     # -- construction -------------------------------------------------------
     @classmethod
@@ -61,6 +63,7 @@ class DeviceBins:
         nat.call("pbx_profile_set_x", self._h, nat.dptr(a), a.shape[0])
         self.n = a.shape[0]
         self.has_selection = False
+        self._kin = None  # (a new x clears the registration)
         self.nbins = None
         self._csr = None
 
@@ -79,6 +82,7 @@ class DeviceBins:
         """
         d = into if into is not None else cls()
         d.nbins, d._csr = None, None
+        d._kin = None  # (a new selection clears the registration)
         # float32 snapshots stay float32 (no host up-cast; pbx_profile_select_typed)
         d._pos_dt = PBX_F32 if (not on_device and np.asarray(pos).dtype == np.float32) else PBX_F64
         d._mass_dt = (PBX_F32 if (not on_device and mass is not None and
@@ -170,6 +174,7 @@ class DeviceBins:
             return d, edges, counts, [m.copy() for m in mom]
         d = into if into is not None else cls()
         d.nbins, d._csr = None, None
+        d._kin = None  # (a new selection clears the registration)
         nq = int(nbins) + 1
         k = len(stats)
         # The selection and statistics arguments of a repeated call on device
@@ -495,6 +500,80 @@ class DeviceBins:
                  nat.dptr(out))
         return out
 
+    # -- kinematic fields ---------------------------------------------------
+    @staticmethod
+    def SRC_KIN(name: str) -> int:  # noqa: N802 - reads like the SRC_* constants
+        """Source selector of a kinematic field (``moments`` / ``percentiles``
+        field argument): vr, vtheta, vphi, vrxy, v2 or vt, computed on the
+        device from the registered positions and velocities."""
+        try:
+            return nat.SRC_KIN + KINEMATIC_FIELDS.index(name)
+        except ValueError:
+            raise ValueError(f"{name!r} is not a kinematic field {KINEMATIC_FIELDS}") from None
+
+    def set_kinematics(self, pos, vel, *, on_device: bool = False, n: int | None = None) -> None:
+        """Register the ORIGINAL particles' positions and velocities, (N,3)
+        float64 with N the length of the arrays the selection was made from
+        (a ``from_x`` handle: its own length, element i = particle i).
+
+        Host arrays are staged into the handle (the span the selection
+        covers); references are kept until the next selection.  Device
+        pointers (``on_device=True``, then ``n`` is required) are borrowed:
+        they must stay allocated and unchanged until the next selection on
+        this handle or ``set_kinematics(None, None)``, which clears the
+        registration (pbx.h, pbx_profile_set_kinematics)."""
+        if pos is None and vel is None:
+            nat.call("pbx_profile_set_kinematics", self._h, None, None, 0, 0)
+            self._kin = None
+            return
+        if on_device:
+            nat.call("pbx_profile_set_kinematics", self._h, pos, vel, int(n), 1)
+            self._kin = (pos, vel)
+            return
+        arrs = []
+        for a in (pos, vel):
+            a = np.ascontiguousarray(np.asarray(a), dtype=np.float64)
+            if a.ndim != 2 or a.shape[1] != 3:
+                raise ValueError("pos and vel must be (N,3)")
+            arrs.append(a)
+        if arrs[0].shape != arrs[1].shape:
+            raise ValueError("pos and vel must have the same shape")
+        nat.call("pbx_profile_set_kinematics", self._h, nat.vptr(arrs[0]), nat.vptr(arrs[1]),
+                 arrs[0].shape[0], 0)
+        self._kin = tuple(arrs)
+
+    @property
+    def has_kinematics(self) -> bool:
+        return getattr(self, "_kin", None) is not None
+
+    def kinematic_field(self, name: str) -> np.ndarray:
+        """The field of the kept particles, in selection order (host array)."""
+        code = self.SRC_KIN(name) - nat.SRC_KIN
+        out = np.empty(self.n)
+        nat.call("pbx_profile_kinematic_field", self._h, code, nat.dptr(out))
+        return out
+
+    def kinematic_moments(self, fields, weights=SRC_NONE, cols=ALL_COLS) -> np.ndarray:
+        """Per-bin sums (len(fields), nbins, 7) of several kinematic fields
+        from one pass over the selection (pbx_profile_kinematic_moments).
+        cols: one column mask for all, or one per field; weights as in
+        ``moments``."""
+        if self.nbins is None:
+            raise ValueError("assign() first")
+        fields = list(fields)
+        nf = len(fields)
+        codes = (c_int * max(nf, 1))(*[self.SRC_KIN(f) - nat.SRC_KIN for f in fields])
+        if isinstance(cols, (int, np.integer)):
+            cols = [cols] * nf
+        if len(cols) != nf:
+            raise ValueError("one column mask per field")
+        cs = (c_uint32 * max(nf, 1))(*[int(c) & ALL_COLS for c in cols])
+        ws, wa = self._src(weights) if weights is not None else (SRC_NONE, None)
+        out = np.zeros((nf, self.nbins, NMOM))
+        nat.call("pbx_profile_kinematic_moments", self._h, nf, codes, ws, self._ptr(wa), cs,
+                 nat.dptr(out))
+        return out
+
     def close(self) -> None:
         if self._h is not None and self._h.value and nat._lib is not None:
             try:
@@ -508,3 +587,6 @@ class DeviceBins:
             self.close()
         except Exception:
             pass
+
+
+SRC_KIN = DeviceBins.SRC_KIN  # SRC_KIN("vr"): the selector of a kinematic field

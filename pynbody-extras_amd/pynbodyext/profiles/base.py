@@ -21,8 +21,9 @@ import numpy as np
 
 from ..calculate import CalculatorBase
 from ..simcore import PendingField, SimSnap, SubSnap
-from ._device import DeviceBins
+from ._device import KINEMATIC_FIELDS, DeviceBins
 from .bins import BinsSet
+from .proarray import kinematics_source, register_kinematics
 from .profile import ProfileBase
 from .spatial_profile import RadialProfile
 
@@ -123,6 +124,20 @@ class RadialProfileBuilder(ProfileBuilderBase):
             sub._pending[key] = fetch_x
             if wdev:
                 sub._pending["mass"] = lambda dev=dev: dev.selection(idx=False, x=False, w=True)[2]
+            # the kinematic fields are derived on the device from the
+            # snapshot's positions and velocities: statistics never read a
+            # column onto the host, sub["vr"] reads the kept particles' only
+            root = kinematics_source(sub, dev)
+            if root is not None:
+                def fetch_kin(name, dev=dev, root=root, idx=idx):
+                    if name in root._arrays:  # (a user array stored since wins)
+                        return root._arrays[name][idx]
+                    register_kinematics(dev, root)
+                    return dev.kinematic_field(name)
+
+                for name in KINEMATIC_FIELDS:
+                    if name not in root._arrays:
+                        sub._pending[name] = lambda name=name: fetch_kin(name)
             xs = PendingField(sub, key)
         else:
             xs = sub[key]

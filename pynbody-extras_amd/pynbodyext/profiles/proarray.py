@@ -15,6 +15,12 @@ device too (segmented radix sort by bin and value, the reference's
 sequential weight cumsum and np.interp per bin, pbx_profile_percentiles);
 user-registered statistics run the reference's per-bin loop over the
 device-built bin index lists.
+
+Kinematic fields (``vr``, ``vtheta``, ``vphi``, ``vrxy``, ``v2``, ``vt``) of
+the project's own float64 snapshots are not read from a host column: the
+device derives them from the root snapshot's positions and velocities
+(``SRC_KIN``, registered once per device handle), and ``beta`` takes its
+three fields from one fused pass (:func:`prefetch_kinematics`).
 """
 from __future__ import annotations
 
@@ -25,8 +31,8 @@ from typing import Union
 import numpy as np
 
 from .._pyn import IndexedSimArray, SimArray
-from ..simcore import PendingField, is_pending
-from ._device import SRC_HOST, SRC_NONE, SRC_W, SRC_X
+from ..simcore import PendingField, SimSnap, SubSnap, is_pending
+from ._device import KINEMATIC_FIELDS, SRC_HOST, SRC_KIN, SRC_NONE, SRC_W, SRC_X
 
 __all__ = ["ProfileArray", "StatisticBase", "Mean", "Sum", "Sum_w", "Percentile", "RMS", "Median",
            "Abs", "Dispersion"]
@@ -235,23 +241,107 @@ def _percentile_of(calc):
     return None
 
 
+def kinematics_source(sim, dev):
+    """The root snapshot whose positions and velocities give the kinematic
+    fields of ``sim``'s particles through ``dev``'s indices, or None.
+
+    The device computes them for the project's own snapshots
+    (simcore.SimSnap) with float64 (N,3) ``pos`` and ``vel``, when the
+    handle's particles are the root's: a fused selection made from the root
+    (``sim`` its view), or the root itself (identity indices).  Anything else
+    — real pynbody snapshots, float32 arrays, views of views — takes the host
+    array, so that ``sim["vtheta"]`` and the profile agree."""
+    root = getattr(sim, "ancestor", None)
+    if not isinstance(root, SimSnap) or isinstance(root, SubSnap):
+        return None
+    if dev.has_selection:
+        if not (isinstance(sim, SubSnap) and sim._base is root and dev.n == len(sim)):
+            return None
+    elif sim is not root or dev.n != len(root):
+        return None
+    pos, vel = root._arrays.get("pos"), root._arrays.get("vel")
+    for a in (pos, vel):
+        if a is None or a.dtype != np.float64 or a.shape != (len(root), 3):
+            return None
+    return root
+
+
+def _stored(sim, name) -> bool:
+    """``name`` is an array the user stored in the view or one of its bases."""
+    while isinstance(sim, SubSnap):
+        if name in sim._arrays:
+            return True
+        sim = sim._base
+    return name in sim._arrays
+
+
+def register_kinematics(dev, root) -> None:
+    """Register the root's positions and velocities once per device handle."""
+    if not dev.has_kinematics:
+        dev.set_kinematics(root._arrays["pos"], root._arrays["vel"])
+
+
+def _kinematic_selector(profile, dev, name):
+    """SRC_KIN(name) when the device derives the field itself, else None."""
+    if name not in KINEMATIC_FIELDS or _stored(profile.sim, name):
+        return None
+    root = kinematics_source(profile.sim, dev)
+    if root is None:
+        return None
+    register_kinematics(dev, root)
+    return SRC_KIN(name)
+
+
+def _weight_source(profile, dev):
+    if not profile._weighted:
+        return SRC_NONE
+    if getattr(profile, "_device_weight_name", None) is not None and dev.has_selection:
+        return SRC_W
+    return np.asarray(profile._weight, dtype=np.float64)
+
+
 def _sources_for(profile, dev, name, arr_pp):
     """Device source selectors (or host arrays) of a field and the weights
     (arr_pp None: the field is device-held and not on the host yet)."""
     bins = profile.bins
+    kin = _kinematic_selector(profile, dev, name) if name is not None else None
     if name is not None and isinstance(bins.bins_by, str) and name == bins.bins_by:
         fsrc = SRC_X
     elif name is not None and dev.has_selection and name == getattr(profile, "_device_weight_name", None):
         fsrc = SRC_W
+    elif kin is not None:
+        fsrc = kin
     else:
         fsrc = np.asarray(profile.sim[name] if arr_pp is None else arr_pp, dtype=np.float64)
-    if not profile._weighted:
-        wsrc = SRC_NONE
-    elif getattr(profile, "_device_weight_name", None) is not None and dev.has_selection:
-        wsrc = SRC_W
-    else:
-        wsrc = np.asarray(profile._weight, dtype=np.float64)
-    return fsrc, wsrc
+    return fsrc, _weight_source(profile, dev)
+
+
+def prefetch_kinematics(profile, names, modes) -> None:
+    """The statistics ``modes`` (functions of per-bin sums) of several
+    kinematic fields from ONE fused device pass (kinematic_moments), put in
+    the profile's statistics cache.  Does nothing when the device does not
+    derive the fields (the statistics are then evaluated one by one)."""
+    dev = getattr(profile.bins, "_device", None)
+    if dev is None or dev.nbins != profile.nbins:
+        return
+    calcs = [ProfileArray.get_statistic(m) for m in modes]
+    if any(c is None or not hasattr(c, "from_moments") for c in calcs):
+        return
+    names = [n for n in names if not all(profile.is_cached(n, c.key) for c in calcs)]
+    if not names or any(_kinematic_selector(profile, dev, n) is None for n in names):
+        return
+    weighted = profile._weighted
+    cols = 0
+    for c in calcs:
+        cols |= _columns_of(c.from_moments, profile.nbins, weighted)
+    mom = dev.kinematic_moments(names, _weight_source(profile, dev), cols)
+    counts = np.asarray(profile.npart_bins)
+    for k, name in enumerate(names):
+        for c in calcs:
+            vals = np.asarray(c.from_moments(mom[k], counts, weighted), dtype=np.float64).view(SimArray)
+            vals.units = profile.sim._unit_of(name)
+            vals.sim = profile.sim
+            profile.cache(ProfileArray(profile, name=name, array=vals, mode=c.key))
 
 
 def _moments_for(profile, dev, name, arr_pp, cols=(1 << 7) - 1) -> np.ndarray:

@@ -48,4 +48,10 @@ def beta(pro):
     if pro.bins.bins_by not in ("r",):
         logger.warning("Beta parameter is useful for spherical systems. Consider using "
                        "RadialProfile with ndim=3")
+    # one fused device pass for the three fields (their rms, and the mean that
+    # pro[field] itself evaluates) when the device derives them; the
+    # expression below then reads the statistics cache
+    from .proarray import prefetch_kinematics
+
+    prefetch_kinematics(pro, ("vphi", "vtheta", "vr"), ("mean", "rms"))
     return 1 - (pro["vphi"]["rms"] ** 2 + pro["vtheta"]["rms"] ** 2) / (2 * pro["vr"]["rms"] ** 2)

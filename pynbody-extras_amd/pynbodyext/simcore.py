@@ -231,6 +231,47 @@ def get_family(name, create: bool = False) -> Family:
 
 
 # --------------------------------------------------------------------------
+# kinematic fields
+# --------------------------------------------------------------------------
+# pynbody's derived velocity arrays, by field code (include/pbx.h PBX_KIN_*)
+KINEMATIC_FIELDS = ("vr", "vtheta", "vphi", "vrxy", "v2", "vt")
+
+
+def kinematic_field(key: str, pos, vel) -> np.ndarray:
+    """One of KINEMATIC_FIELDS from (N,3) positions and velocities.
+
+    The expressions and their order are the contract the device kernels
+    (csrc/profile.hip, kin_fields) share, so that both give the same bits:
+    vr, vrxy, vphi, v2 and vt are pynbody's; vtheta is the algebraic form of
+    pynbody's trigonometric one (cos az = x/rxy, cos theta = z/r, sin theta =
+    rxy/r).  On the z axis and at the origin 0/0 is NaN, and vt is NaN where
+    rounding makes v2 - vr*vr negative: numpy's values, kept."""
+    x, y, z = pos[:, 0], pos[:, 1], pos[:, 2]
+    vx, vy, vz = vel[:, 0], vel[:, 1], vel[:, 2]
+    with np.errstate(all="ignore"):
+        if key == "v2":
+            return (vx * vx + vy * vy) + vz * vz
+        rxy2 = x * x + y * y
+        r2 = rxy2 + z * z
+        rxy, r = np.sqrt(rxy2), np.sqrt(r2)
+        if key == "vphi":
+            return (x * vy - y * vx) / rxy
+        s = x * vx + y * vy
+        if key == "vrxy":
+            return s / rxy
+        if key == "vtheta":
+            vrxy = s / rxy
+            return (z * vrxy - rxy * vz) / r
+        vr = (s + z * vz) / r
+        if key == "vr":
+            return vr
+        if key == "vt":
+            v2 = (vx * vx + vy * vy) + vz * vz
+            return np.sqrt(v2 - vr * vr)
+    raise KeyError(key)
+
+
+# --------------------------------------------------------------------------
 # snapshots
 # --------------------------------------------------------------------------
 class SimSnap:
@@ -289,6 +330,12 @@ class SimSnap:
             p = self._array("pos")
             x, y = p[:, 0], p[:, 1]
             val = np.sqrt(x * x + y * y)
+        elif key in KINEMATIC_FIELDS:
+            try:
+                p, v = self._array("pos"), self._array("vel")
+            except KeyError:
+                raise KeyError(key) from None
+            val = kinematic_field(key, p, v)
         else:
             raise KeyError(key)
         self._derived[key] = val
@@ -301,6 +348,8 @@ class SimSnap:
             return self._units["pos"]
         if key in ("vx", "vy", "vz") and "vel" in self._units:
             return self._units["vel"]
+        if key in KINEMATIC_FIELDS and "vel" in self._units:
+            return self._units["vel"] ** 2 if key == "v2" else self._units["vel"]
         return NoUnit
 
     def __setitem__(self, key: str, value):
