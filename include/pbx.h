@@ -522,6 +522,86 @@ int pbx_profile_set_level0_hint(void *handle, int enabled);
 int pbx_profile_percentiles(void *handle, int f_src, const double *h_f, int w_src,
                             const double *h_w, int absval, int nq, const double *q,
                             double *h_out);
+/* The containment values of the handle's whole x as ONE group — replaces
+ * ParamContain.calculate (properties/base.py:60-103): the stable sort of x
+ * by value (the percentiles' key sort, no bin-id sort and no assignment),
+ * cumsum of the weights in that order, h_out[k] = np.interp(q[k],
+ * (cumsum - cumsum[0]) / denom, sorted x) with *denom = cumsum[-1] -
+ * cumsum[0].  Runs after a selection or after pbx_profile_set_x; w_src = 1
+ * (the selection weights) or 2 (the host array h_w, n doubles in selection
+ * order); 1 <= nq <= 4096.  With fewer than 2 elements or denom <= 0, h_out
+ * is not meaningful (*denom = 0 below 2 elements) and the status is still
+ * PBX_OK: the caller raises the reference's error.  Ties keep index order
+ * (the reference's default np.argsort leaves their order open).  The
+ * cumulative sum runs sequentially on one lane on purpose: that reproduces
+ * np.cumsum's rounding bit for bit.  Its cost grows linearly with the
+ * selection and is unmeasured; a parallel scan would trade the bit parity
+ * away and is left for later. */
+int pbx_profile_contain(void *handle, int w_src, const double *h_w, int nq, const double *q,
+                        double *h_out, double *denom);
+
+/* ------------------------------------------------------------------ */
+/* scalar properties: one streaming pass over a selection              */
+/* ------------------------------------------------------------------ */
+/* Replaces the numpy passes of pynbodyext/properties (properties/generic.py:
+ * 39-198: CenPos, CenVel, AngMomVec, KappaRot, KappaRotMean, PatternSpeed;
+ * properties/base.py:60-119: ParamContain, ParamSum).  A particle is kept
+ * exactly as pbx_profile_select keeps it (family ranges, strict Sphere
+ * test); for every kept particle a count and the sums of the requested
+ * groups are accumulated in float64, every term evaluated without FMA
+ * contraction in the order written here (m = mass, or 1.0 when mass is
+ * NULL), with
+ *   vc = (x*vy - y*vx) / sqrt(x*x + y*y);  ke = 0.5*((vx*vx + vy*vy) + vz*vz)
+ * (0/0 on the z axis and ke == 0 give NaN / inf as numpy does, and they
+ * propagate into the sum; a particle that is not kept contributes nothing,
+ * whatever its values):
+ *   group                sums    terms
+ *   PBX_PROP_MASS        0       m
+ *   PBX_PROP_COM         1-3     x*m, y*m, z*m
+ *   PBX_PROP_COV         4-6     vx*m, vy*m, vz*m
+ *   PBX_PROP_ANGMOM      7-9     m*(y*vz - z*vy), m*(z*vx - x*vz), m*(x*vy - y*vx)
+ *   PBX_PROP_KAPPA       10, 11  (0.5*m)*(vc*vc), m*ke
+ *   PBX_PROP_KAPPA_MEAN  12      (0.5*(vc*vc))/ke
+ *   PBX_PROP_PATTERN     13-17   (m*x)*x, (m*y)*y, (m*x)*y, m*(x*vy + y*vx),
+ *                                m*(x*vx - y*vy)
+ * The order of summation is fixed by the particle count alone (no atomics):
+ * the same call gives the same bits, and a sum's bits do not depend on which
+ * other groups are requested. */
+#define PBX_PROP_MASS 1
+#define PBX_PROP_COM 2
+#define PBX_PROP_COV 4
+#define PBX_PROP_ANGMOM 8
+#define PBX_PROP_KAPPA 16
+#define PBX_PROP_KAPPA_MEAN 32
+#define PBX_PROP_PATTERN 64
+#define PBX_PROP_NSUMS 18
+/* Stateless; pos / vel (n x 3) and mass (n, may be NULL) are host arrays
+ * (only the span the families cover is staged) or device pointers
+ * (on_device = 1); sphere, fam and nfam as in pbx_profile_select.  vel is
+ * read only for a velocity group, pos only for a sphere or a position group
+ * (either may be NULL otherwise).  h_sums[PBX_PROP_NSUMS]: unrequested sums
+ * are 0.0; nothing kept: *n_kept = 0, all sums 0.0, PBX_OK.  PBX_ERR_VALUE:
+ * groups == 0 or unknown bits, a needed array NULL, n < 0, nfam > 16. */
+int pbx_property_moments(const double *pos, const double *vel, const double *mass, int64_t n,
+                         int on_device, int use_sphere, const double *sphere,
+                         const int64_t *fam, int nfam, uint32_t groups, int64_t *n_kept,
+                         double *h_sums);
+/* Shrinking-sphere centre of the particles in the family ranges (all when
+ * nfam = 0) — the centre CenPos("ssc") asks pynbody for
+ * (properties/generic.py:54-55).  The particles are staged once (or
+ * borrowed, on_device = 1) and the pass above runs with groups MASS | COM
+ * and a moving sphere, one read-back per iteration:
+ *   com = sum(m*pos) / sum(m) over the particles;  r = r0
+ *   repeat: keep = ((dx*dx + dy*dy) + dz*dz) < r*r about com;  c = count(keep)
+ *           if c <= min_particles: stop (com unchanged)
+ *           com = sum_keep(m*pos) / sum_keep(m);  r *= shrink_factor
+ * h_cen[3] = com, *iterations = completed shrink steps, *n_last = the
+ * particle count the returned centre was computed from.  PBX_ERR_VALUE: r0
+ * <= 0 or NaN, shrink_factor outside (0, 1), min_particles < 1. */
+int pbx_property_shrink_center(const double *pos, const double *mass, int64_t n, int on_device,
+                               const int64_t *fam, int nfam, double r0, double shrink_factor,
+                               int64_t min_particles, double *h_cen, int64_t *iterations,
+                               int64_t *n_last);
 
 /* ------------------------------------------------------------------ */
 /* multi-GPU: RCCL communicator (one process per GPU, over xGMI)       */

@@ -114,6 +114,10 @@ enum Slot {
   kSlotSymAcc,
   kSlotSymUnits,
   kSlotSymProbe,
+  kSlotPropPos,
+  kSlotPropVel,
+  kSlotPropMass,
+  kSlotPropPart,
   kSlotCount
 };
 

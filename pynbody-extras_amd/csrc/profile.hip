@@ -7129,4 +7129,59 @@ int pbx_profile_radial_equaln_comm(void *comm, void *handle, const double *pos, 
                                        h_counts_local});
 }
 
+// Containment values of the handle's whole x as one group (ParamContain,
+// properties/base.py:83-103): percentiles_device's stable value sort
+// (pct_keys + eight radix passes; no bin-id sort, no assignment), then
+// pct_bins with the single offset pair {0, n}.  *denom = cumsum[-1] -
+// cumsum[0] of the weights in value order (pct_bins' sequential cumsum:
+// np.cumsum's rounding).
+int pbx_profile_contain(void *handle, int w_src, const double *h_w, int nq, const double *q,
+                        double *h_out, double *denom) {
+  return with_profile(handle, [&](Profile &P, Device &d, hipStream_t st) {
+    if (nq < 1 || nq > 4096) fail(PBX_ERR_VALUE, "1 to 4096 fractions per call");
+    if (w_src != 1 && w_src != 2)
+      fail(PBX_ERR_VALUE, "w_src must be 1 (selection weights) or 2 (host array)");
+    if (!q || !h_out || !denom) fail(PBX_ERR_VALUE, "null argument");
+    ScopedTimer tm("pbx.profile.contain");
+    const int64_t n = P.n;
+    *denom = 0.0;
+    const double *f = resolve_src(P, st, 0, nullptr, P.field);
+    const double *w = resolve_src(P, st, w_src, h_w, P.weight);
+    if (n == 0) {
+      PBX_HIP(hipStreamSynchronize(st));
+      return;
+    }
+    double *dq = (double *)P.pq.get(sizeof(double) * (size_t)nq);
+    PBX_HIP(hipMemcpyAsync(dq, q, sizeof(double) * nq, hipMemcpyHostToDevice, st));
+    const int64_t h_off[2] = {0, n};  // (alive until the sync below)
+    int64_t *off = (int64_t *)P.poff.get(sizeof(int64_t) * 2);
+    PBX_HIP(hipMemcpyAsync(off, h_off, sizeof(h_off), hipMemcpyHostToDevice, st));
+    uint64_t *ka = (uint64_t *)P.pk0.get(sizeof(uint64_t) * (size_t)n);
+    uint64_t *kb = (uint64_t *)P.pk1.get(sizeof(uint64_t) * (size_t)n);
+    int32_t *va = (int32_t *)P.pv0.get(sizeof(int32_t) * (size_t)n);
+    int32_t *vb = (int32_t *)P.pv1.get(sizeof(int32_t) * (size_t)n);
+    hipLaunchKernelGGL(pct_keys, dim3(ceil_div(n, TPB)), dim3(TPB), 0, st, f, n, 0, ka);
+    for (int shift = 0; shift < 64; shift += 8) {
+      const bool last = shift + 8 >= 64;
+      prim::radix_pass<uint64_t>(P.hist, P.tsum, st, ka, shift == 0 ? nullptr : va,
+                                 shift == 0 ? VAL_IOTA : VAL_ARRAY, n, shift, last ? nullptr : kb, vb);
+      std::swap(ka, kb);
+      std::swap(va, vb);
+    }
+    double *cdf = (double *)P.pcdf.get(sizeof(double) * (size_t)n);
+    double *out = (double *)P.pout.get(sizeof(double) * (size_t)nq);
+    hipLaunchKernelGGL(pct_bins, dim3(1), dim3(TPB), 0, st, (const int32_t *)va,
+                       (const int64_t *)off, f, w, 0, (const double *)dq, nq, cdf, out);
+    PBX_HIP(hipGetLastError());
+    double c[2] = {0.0, 0.0};
+    PBX_HIP(hipMemcpyAsync(h_out, out, sizeof(double) * nq, hipMemcpyDeviceToHost, st));
+    if (n >= 2) {  // (pct_bins writes the cumulative sum from two elements on)
+      PBX_HIP(hipMemcpyAsync(&c[0], cdf, sizeof(double), hipMemcpyDeviceToHost, st));
+      PBX_HIP(hipMemcpyAsync(&c[1], cdf + (n - 1), sizeof(double), hipMemcpyDeviceToHost, st));
+    }
+    PBX_HIP(hipStreamSynchronize(st));
+    *denom = c[1] - c[0];
+  });
+}
+
 }  // extern "C"

@@ -4,6 +4,7 @@ from __future__ import annotations
 try:  # pragma: no cover - pynbody is absent in this image
     import pynbody as _pynbody
     from pynbody import filt, units
+    from pynbody.analysis.halo import shrink_sphere_center
     from pynbody.array import IndexedSimArray, SimArray
     from pynbody.family import Family, get_family
     from pynbody.snapshot import SimSnap
@@ -17,10 +18,11 @@ except ImportError:
         SimSnap,
         filt,
         get_family,
+        shrink_sphere_center,
         units,
     )
 
     HAVE_PYNBODY = False
 
 __all__ = ["SimArray", "IndexedSimArray", "SimSnap", "Family", "get_family", "units", "filt",
-           "HAVE_PYNBODY"]
+           "shrink_sphere_center", "HAVE_PYNBODY"]

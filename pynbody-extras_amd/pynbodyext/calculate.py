@@ -13,7 +13,12 @@ through, with the same names and semantics:
   context.py:610-646),
 * ``FilterBase`` with ``&``, ``|``, ``~`` composition (filters.py:124-313),
 * ``RunOptions`` / ``ExecutionContext.phase`` / dynamic parameters
-  (context.py:503-533, base.py:422).
+  (context.py:503-533, base.py:422),
+* ``PropertyBase`` with ``calculate(sim, params)``, the declarative
+  ``PropertyBase.dataclass`` / ``Param`` fields and host-side arithmetic
+  (``+ - * /``, unary ``-``) into ``OpProperty`` / ``ConstantProperty``
+  (properties.py:125-295, fields.py:29-125, expr.py:117-260); comparisons,
+  ``clip``, caching, tracing and pipelines are not provided.
 
 MI355X addition: a calculator may implement ``execute_fused(ctx, input,
 filt)``; a bound calculator offers it its filter first, so a radial profile
@@ -23,6 +28,8 @@ pipeline instead of materialising the masked snapshot on the host.
 from __future__ import annotations
 
 import copy
+import dataclasses
+import operator
 import time
 from contextlib import contextmanager
 from dataclasses import dataclass, field
@@ -32,7 +39,8 @@ import numpy as np
 
 __all__ = ["RunOptions", "Result", "NodeInput", "ExecutionContext", "CalculatorBase",
            "BoundCalculator", "FilterBase", "AndFilter", "OrFilter", "NotFilter",
-           "resolve_value_in_units"]
+           "resolve_value_in_units", "Param", "ParamView", "PropertyBase", "ConstantProperty",
+           "OpProperty"]
 
 
 @dataclass
@@ -288,3 +296,189 @@ def _intersect_ranges(a, b):
             if hi > lo:
                 out.append((lo, hi))
     return out
+
+
+# --------------------------------------------------------------------------
+# properties
+# --------------------------------------------------------------------------
+class Param:
+    """Marks a dynamic parameter of a declarative property
+    (``frac: Param[float] = Param(default=0.5)``): a constant, a unit string
+    (converted to the units of ``sim[field_name]``), a callable of the
+    snapshot or another calculator, resolved when the property runs."""
+
+    def __init__(self, default=dataclasses.MISSING, *, field_name: str | None = None):
+        self.default = default
+        self.field_name = field_name
+
+    def __class_getitem__(cls, item):
+        return cls
+
+
+class ParamView:
+    """The parameters ``calculate`` receives: the instance's fields with the
+    dynamic ones resolved, by attribute or by item."""
+
+    def __init__(self, values: dict):
+        self.__dict__.update(values)
+
+    def __getitem__(self, key):
+        return self.__dict__[key]
+
+    def __contains__(self, key):
+        return key in self.__dict__
+
+    def __repr__(self):
+        return f"ParamView({self.__dict__!r})"
+
+
+class PropertyBase(CalculatorBase):
+    """Calculator reading one value from the active snapshot
+    (reference core/calculate/properties.py:125).
+
+    Subclasses implement ``calculate(sim, params=None)``.  MI355X addition: a
+    property may implement ``device_plan(source, spec, params)``; on a root
+    snapshot (unfiltered, or behind a filter scope the device understands) it
+    then runs as one pass over the snapshot's arrays on the device instead
+    of numpy passes over the masked sub-snapshot (pynbodyext/properties)."""
+
+    def __class_getitem__(cls, item):
+        return cls
+
+    @classmethod
+    def dataclass(cls, target=None, **dataclass_kwargs):
+        """``dataclasses.dataclass`` for a property class; ``Param`` fields
+        become ordinary fields with the Param's default and are recorded as
+        dynamic parameters."""
+        def wrap(t):
+            specs = dict(getattr(t, "dynamic_param_specs", {}))
+            for name, v in list(vars(t).items()):
+                if isinstance(v, Param):
+                    specs[name] = v.field_name
+                    if v.default is dataclasses.MISSING:
+                        delattr(t, name)
+                    else:
+                        setattr(t, name, v.default)
+            t.dynamic_param_specs = specs
+            dataclass_kwargs.setdefault("eq", False)  # identity hash, no truth-valued ==
+            return dataclasses.dataclass(t, **dataclass_kwargs)
+
+        return wrap if target is None else wrap(target)
+
+    # -- evaluation ------------------------------------------------------------
+    def calculate(self, sim, params=None):
+        raise NotImplementedError(f"{type(self).__name__} must implement calculate()")
+
+    def _params(self, ctx: ExecutionContext, input: NodeInput) -> ParamView:
+        values = {}
+        if dataclasses.is_dataclass(self):
+            values = {f.name: getattr(self, f.name) for f in dataclasses.fields(self)}
+        values.update(self.resolve_dynamic_params(ctx, input))
+        return ParamView(values)
+
+    def device_plan(self, source, spec: dict, params: ParamView):
+        """A zero-argument callable evaluating this property on the device
+        for the root snapshot ``source`` restricted by ``spec`` (a filter's
+        ``device_spec``; {} = every particle), or None: no device route."""
+        return None
+
+    def _device_route(self, ctx: ExecutionContext, input: NodeInput, spec: dict):
+        if type(self).device_plan is PropertyBase.device_plan:
+            return NotImplemented
+        # dynamic parameters are resolved on the snapshot the caller scoped:
+        # one that depends on it keeps the two-step semantics behind a filter
+        if spec and any(callable(getattr(self, k, None)) for k in self.dynamic_param_specs):
+            return NotImplemented
+        plan = self.device_plan(input.source_sim, spec, self._params(ctx, input))
+        if plan is None:
+            return NotImplemented
+        with ctx.phase(self, "device"):
+            return plan()
+
+    def execute(self, ctx: ExecutionContext, input: NodeInput):
+        if input.mask is None:
+            res = self._device_route(ctx, input, {})
+            if res is not NotImplemented:
+                return res
+        sim = input.active_sim
+        params = self._params(ctx, input)
+        with ctx.phase(self, "calculate"):
+            return self.calculate(sim, params)
+
+    def execute_fused(self, ctx: ExecutionContext, input: NodeInput, filt: "FilterBase"):
+        spec = filt.device_spec(input.source_sim)
+        if spec is None:
+            return NotImplemented
+        return self._device_route(ctx, input, spec)
+
+    # -- host-side arithmetic --------------------------------------------------
+    @classmethod
+    def as_property(cls, other) -> "PropertyBase":
+        return other if isinstance(other, PropertyBase) else ConstantProperty(other)
+
+    def __add__(self, other):
+        return OpProperty("add", self, self.as_property(other))
+
+    def __radd__(self, other):
+        return OpProperty("add", self.as_property(other), self)
+
+    def __sub__(self, other):
+        return OpProperty("sub", self, self.as_property(other))
+
+    def __rsub__(self, other):
+        return OpProperty("sub", self.as_property(other), self)
+
+    def __mul__(self, other):
+        return OpProperty("mul", self, self.as_property(other))
+
+    def __rmul__(self, other):
+        return OpProperty("mul", self.as_property(other), self)
+
+    def __truediv__(self, other):
+        return OpProperty("truediv", self, self.as_property(other))
+
+    def __rtruediv__(self, other):
+        return OpProperty("truediv", self.as_property(other), self)
+
+    def __neg__(self):
+        return OpProperty("neg", self)
+
+    __hash__ = object.__hash__
+
+    def __bool__(self) -> bool:
+        raise TypeError("PropertyBase is symbolic; evaluate with run() or value().")
+
+
+class ConstantProperty(PropertyBase):
+    """A constant as a property (reference expr.py:117)."""
+
+    def __init__(self, value):
+        self.value_ = value
+
+    def calculate(self, sim, params=None):
+        return self.value_
+
+    def __repr__(self):
+        return f"ConstantProperty({self.value_!r})"
+
+
+class OpProperty(PropertyBase):
+    """``op`` applied on the host to the values of its operands, each
+    evaluated on the same input (reference expr.py:199)."""
+
+    _OPS = {"add": operator.add, "sub": operator.sub, "mul": operator.mul,
+            "truediv": operator.truediv, "neg": operator.neg}
+
+    def __init__(self, op_name: str, *operands: PropertyBase):
+        if op_name not in self._OPS:
+            raise ValueError(f"unknown operator {op_name!r}")
+        self.op_name = op_name
+        self.operands = operands
+
+    def execute(self, ctx: ExecutionContext, input: NodeInput):
+        values = [ctx.public_value(o, input) for o in self.operands]
+        with ctx.phase(self, "calculate"):
+            return self._OPS[self.op_name](*values)
+
+    def __repr__(self):
+        return f"OpProperty({self.op_name!r}, {', '.join(map(repr, self.operands))})"

@@ -470,6 +470,22 @@ class DeviceBins:
                  int(bool(absval)), qa.shape[0], nat.dptr(qa), nat.dptr(out))
         return out
 
+    def contain(self, q, weights=SRC_W) -> tuple[np.ndarray, float]:
+        """(values, denom): the containment values of the handle's WHOLE x as
+        one group — np.interp(q, (cumsum(w) - cumsum(w)[0]) / denom, sorted x)
+        with w in stable value order of x and denom = cumsum[-1] - cumsum[0]
+        (pbx_profile_contain; ParamContain of the reference).  weights:
+        SRC_W (the selection's) or a host array of length n.  With fewer than
+        two elements or denom <= 0 the values are not meaningful: the caller
+        raises the reference's error."""
+        qa = np.ascontiguousarray(np.atleast_1d(np.asarray(q, dtype=np.float64)))
+        ws, wa = self._src(weights)
+        out = np.zeros(qa.shape[0])
+        denom = c_double(0.0)
+        nat.call("pbx_profile_contain", self._h, ws, self._ptr(wa), qa.shape[0], nat.dptr(qa),
+                 nat.dptr(out), byref(denom))
+        return out, denom.value
+
     def moments(self, field=SRC_X, weights=SRC_NONE, cols: int = ALL_COLS) -> np.ndarray:
         """Per-bin sums (nbins, 7): Σw, Σf·w, Σf²·w, Σf, Σf², Σ|f|·w, Σ|f|.
 

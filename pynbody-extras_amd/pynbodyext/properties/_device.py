@@ -1,0 +1,148 @@
+"""Device route of the property calculators (libpbx, csrc/property.hip).
+
+Thin ctypes wrappers of pbx_property_moments and pbx_property_shrink_center
+(include/pbx.h, "scalar properties"), and the conditions under which a
+property takes them: the source is a root ``SimSnap`` of the snapshot layer
+whose ``pos`` / ``vel`` / ``mass`` are float64 and C-contiguous and that
+stores no user array named ``vcxy`` or ``ke``.  Everything else runs the
+property's ``calculate`` on the host.
+"""
+from __future__ import annotations
+
+import ctypes
+from ctypes import byref, c_int64, c_void_p
+
+import numpy as np
+
+from .. import _native as nat
+from ..simcore import SimSnap, SubSnap
+
+# group bits and sum layout (pbx.h PBX_PROP_*)
+MASS, COM, COV, ANGMOM, KAPPA, KAPPA_MEAN, PATTERN = 1, 2, 4, 8, 16, 32, 64
+ALL_GROUPS = 127
+NSUMS = 18
+POS_GROUPS = COM | ANGMOM | KAPPA | KAPPA_MEAN | PATTERN
+VEL_GROUPS = COV | ANGMOM | KAPPA | KAPPA_MEAN | PATTERN
+
+_i64p = ctypes.POINTER(c_int64)
+
+
+def _particle_args(arrays, on_device, n):
+    """(pointers, n, keep-alive) of (N,3) / (N,) float64 host arrays or device pointers."""
+    if on_device:
+        return list(arrays), int(n), ()
+    keep, ptrs, count = [], [], None
+    for k, a in enumerate(arrays):
+        if a is None:
+            ptrs.append(None)
+            continue
+        a = np.ascontiguousarray(np.asarray(a), dtype=np.float64)
+        width3 = k < len(arrays) - 1  # (the last one is the mass)
+        if (width3 and (a.ndim != 2 or a.shape[1] != 3)) or (not width3 and a.ndim != 1):
+            raise ValueError("pos and vel must be (N,3), mass (N,)")
+        if count is not None and a.shape[0] != count:
+            raise ValueError("pos, vel and mass must have the same length")
+        count = a.shape[0]
+        keep.append(a)
+        ptrs.append(a.ctypes.data_as(c_void_p))
+    if count is None:
+        count = int(n) if n is not None else 0
+    return ptrs, count, tuple(keep)
+
+
+def _scope_args(sphere, families):
+    """(use_sphere, sphere[4], fam, nfam, keep-alive): a filter's device_spec
+    as pbx_profile_select takes it."""
+    sph = np.zeros(4)
+    if sphere is not None:
+        cen, radius = sphere
+        radius = float(radius)
+        sph[:3] = np.asarray(cen, dtype=np.float64).reshape(3)
+        sph[3] = radius * radius
+    fam = np.zeros(2, dtype=np.int64)
+    nfam = 0
+    if families is not None:
+        fam = np.ascontiguousarray(np.asarray(families, dtype=np.int64).reshape(-1, 2))
+        nfam = fam.shape[0]
+        if nfam == 0:  # an empty family set keeps nothing
+            fam = np.array([[0, 0]], dtype=np.int64)
+            nfam = 1
+    return int(sphere is not None), sph, fam, nfam
+
+
+def moments(pos, vel, mass, *, groups: int, sphere=None, families=None, on_device: bool = False,
+            n: int | None = None) -> tuple[int, np.ndarray]:
+    """(n_kept, sums[18]) of the kept particles in one device pass
+    (pbx_property_moments): the count and the sums of the requested groups,
+    the others 0.0.  pos / vel / mass: host arrays, or device pointers with
+    ``on_device=True`` and ``n``; any of them may be None when no requested
+    group (and no sphere) reads it (mass None: unit masses)."""
+    ptrs, count, keep = _particle_args((pos, vel, mass), on_device, n)
+    use_sphere, sph, fam, nfam = _scope_args(sphere, families)
+    kept = c_int64(0)
+    sums = np.zeros(NSUMS)
+    nat.call("pbx_property_moments", ptrs[0], ptrs[1], ptrs[2], count, int(on_device), use_sphere,
+             nat.dptr(sph), fam.ctypes.data_as(_i64p), nfam, int(groups), byref(kept),
+             nat.dptr(sums))
+    del keep
+    return kept.value, sums
+
+
+def shrink_center(pos, mass, *, r0: float, shrink_factor: float = 0.7, min_particles: int = 100,
+                  families=None, on_device: bool = False,
+                  n: int | None = None) -> tuple[np.ndarray, int, int]:
+    """(centre[3], iterations, n_last): the shrinking-sphere centre of the
+    particles in the family ranges, the loop of simcore.shrink_sphere_center
+    driven by the library over data that stays on the device
+    (pbx_property_shrink_center)."""
+    ptrs, count, keep = _particle_args((pos, mass), on_device, n)
+    _, _, fam, nfam = _scope_args(None, families)
+    cen = np.zeros(3)
+    it, last = c_int64(0), c_int64(0)
+    nat.call("pbx_property_shrink_center", ptrs[0], ptrs[1], count, int(on_device),
+             fam.ctypes.data_as(_i64p), nfam, float(r0), float(shrink_factor), int(min_particles),
+             nat.dptr(cen), byref(it), byref(last))
+    del keep
+    return cen, it.value, last.value
+
+
+# -- routing -------------------------------------------------------------------
+def snapshot_arrays(source, fields) -> dict | None:
+    """The snapshot's arrays of ``fields`` when the device route may read
+    them in place, else None (the property then runs on the host)."""
+    if not isinstance(source, SimSnap) or isinstance(source, SubSnap):
+        return None
+    stored = source._arrays
+    if "vcxy" in stored or "ke" in stored:  # a user's own column wins: host route
+        return None
+    out = {}
+    for f in fields:
+        a = stored.get(f)
+        if a is None or a.dtype != np.float64 or not a.flags.c_contiguous:
+            return None
+        if a.shape != ((len(source), 3) if f in ("pos", "vel") else (len(source),)):
+            return None
+        out[f] = a
+    return out
+
+
+def moments_plan(prop, source, spec: dict):
+    """Device plan of a property declaring ``device_groups`` and
+    ``finish(n_kept, sums, sim)``."""
+    groups = prop.device_groups
+    sphere, families = spec.get("sphere"), spec.get("families")
+    fields = ["mass"] if groups != KAPPA_MEAN else []
+    if sphere is not None or groups & POS_GROUPS:
+        fields.append("pos")
+    if groups & VEL_GROUPS:
+        fields.append("vel")
+    arrs = snapshot_arrays(source, fields)
+    if arrs is None:
+        return None
+
+    def run():
+        n_kept, sums = moments(arrs.get("pos"), arrs.get("vel"), arrs.get("mass"), groups=groups,
+                               sphere=sphere, families=families, n=len(source))
+        return prop.finish(n_kept, sums, source)
+
+    return run

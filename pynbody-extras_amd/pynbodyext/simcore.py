@@ -13,7 +13,11 @@ path needs a stand-in for the few pieces of pynbody its callers touch:
   (pynbody/derived.py evaluates ``(pos**2).sum(axis=1) ** 0.5``, which
   numpy computes as exactly this expression followed by a correctly rounded
   sqrt);
-* ``filt`` — Sphere / FamilyFilter / And / Or / Not masks.
+* ``filt`` — Sphere / FamilyFilter / And / Or / Not masks;
+* what the property calculators read: the derived fields ``vcxy`` (the same
+  expression and bits as ``vphi``) and ``ke = 0.5 * v2``,
+  ``SimSnap.mean_by_mass`` and ``shrink_sphere_center`` (the stand-in for
+  pynbody.analysis.halo's, whose algorithm is restated there).
 
 When the real pynbody is importable, :mod:`pynbodyext._pyn` uses it instead.
 """
@@ -336,6 +340,14 @@ class SimSnap:
             except KeyError:
                 raise KeyError(key) from None
             val = kinematic_field(key, p, v)
+        elif key in ("vcxy", "ke"):
+            # pynbody's vcxy = (-y*vx + x*vy) / sqrt(x**2 + y**2) is vphi's
+            # expression (the same bits); ke = 0.5 * v2
+            try:
+                p, v = self._array("pos"), self._array("vel")
+            except KeyError:
+                raise KeyError(key) from None
+            val = kinematic_field("vphi", p, v) if key == "vcxy" else 0.5 * kinematic_field("v2", p, v)
         else:
             raise KeyError(key)
         self._derived[key] = val
@@ -350,7 +362,17 @@ class SimSnap:
             return self._units["vel"]
         if key in KINEMATIC_FIELDS and "vel" in self._units:
             return self._units["vel"] ** 2 if key == "v2" else self._units["vel"]
+        if key in ("vcxy", "ke") and "vel" in self._units:
+            return self._units["vel"] ** 2 if key == "ke" else self._units["vel"]
         return NoUnit
+
+    def mean_by_mass(self, name: str) -> "SimArray":
+        """Mass-weighted mean of a field: sum(m * a) / sum(m), per column."""
+        m = np.asarray(self["mass"])
+        a = self[name]
+        with np.errstate(all="ignore"):  # (an empty snapshot: 0/0 is NaN, as numpy gives)
+            val = (np.asarray(a).T * m).sum(axis=-1) / m.sum()
+        return SimArray(val, a.units, sim=self)
 
     def __setitem__(self, key: str, value):
         value = np.asarray(value)
@@ -517,6 +539,44 @@ def new_snapshot(pos, mass, families: dict | None = None, units_map: dict | None
     arrs = {"pos": np.asarray(pos, dtype=np.float64), "mass": np.asarray(mass, dtype=np.float64)}
     arrs.update(arrays)
     return SimSnap(arrs, families=families, units_map=units_map)
+
+
+def shrink_sphere_center(sim, r=None, shrink_factor=0.7, min_particles=100, **kwargs) -> SimArray:
+    """Shrinking-sphere centre (the stand-in for
+    pynbody.analysis.halo.shrink_sphere_center, whose source is not part of
+    this package; this statement is the stand-in's contract, DESIGN.md)::
+
+        com = sum(m*pos) / sum(m) over the particles
+        r = r0 (default (x.max() - x.min()) / 2)
+        repeat: keep = ((dx*dx + dy*dy) + dz*dz) < r*r about com;  c = count(keep)
+                if c <= min_particles: stop (com unchanged)
+                com = sum_keep(m*pos) / sum_keep(m);  r *= shrink_factor
+    """
+    pos_sa = sim["pos"]
+    pos = np.asarray(pos_sa)
+    mass = np.asarray(sim["mass"])
+    r = shrink_sphere_r0(sim, r)
+    with np.errstate(all="ignore"):
+        com = (pos.T * mass).sum(axis=1) / mass.sum()
+        while True:
+            dx, dy, dz = pos[:, 0] - com[0], pos[:, 1] - com[1], pos[:, 2] - com[2]
+            keep = ((dx * dx + dy * dy) + dz * dz) < r * r
+            if np.count_nonzero(keep) <= min_particles:
+                break
+            com = (pos[keep].T * mass[keep]).sum(axis=1) / mass[keep].sum()
+            r *= shrink_factor
+    return SimArray(com, pos_sa.units, sim=sim)
+
+
+def shrink_sphere_r0(sim, r=None) -> float:
+    """The initial radius of shrink_sphere_center: ``r`` (a number, or a unit
+    string converted to the position units), default (x.max() - x.min()) / 2."""
+    if r is None:
+        x = np.asarray(sim["x"])
+        return float((x.max() - x.min()) / 2)
+    if isinstance(r, (str, Unit)):
+        return float(as_unit(r).ratio(sim["pos"].units))
+    return float(r)
 
 
 # --------------------------------------------------------------------------
