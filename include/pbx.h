@@ -407,6 +407,38 @@ int pbx_profile_kinematic_field(void *handle, int code, double *h_out);
  * (same results to rounding). */
 int pbx_profile_kinematic_moments(void *handle, int n_fields, const int *codes, int w_src,
                                   const double *h_w, const uint32_t *cols, double *h_out);
+/* The frame a handle reads particles in: an optional position shift c, an
+ * optional velocity shift vc and an optional rotation R (row-major 3 x 3),
+ * packed as frame[15] = {c[3], vc[3], R[9]} with one PBX_FRAME_* flag per
+ * step.  Per particle, in float64 without FMA contraction, in this order:
+ *   dx = x - c0;  dy = y - c1;  dz = z - c2            (PBX_FRAME_POS)
+ *   x' = (R00*dx + R01*dy) + R02*dz;  y' = (R10*dx + R11*dy) + R12*dz;
+ *   z' = (R20*dx + R21*dy) + R22*dz                    (PBX_FRAME_ROT)
+ * and the same for v with vc (PBX_FRAME_VEL, PBX_FRAME_ROT).  A step whose
+ * flag is off is skipped, not run with zeros or the identity (0 * inf would
+ * turn an infinite coordinate into NaN).  Everything downstream is computed
+ * from x', v' exactly as it is from x, v without a frame: the Sphere test of
+ * every selection (its centre is given in frame coordinates), x = r / rxy,
+ * and the kinematic fields (pbx_profile_kinematic_field,
+ * pbx_profile_kinematic_moments, the PBX_SRC_KIN sources).  This replaces
+ * the in-place array rewrites of the reference's transforms
+ * (transforms/shift.py, transforms/rotate.py) for the device passes.
+ * Sticky: the frame stays on the handle across selections (it is a property
+ * of how the handle reads particles) until flags == 0 or frame == NULL
+ * clears it.  Set it before the selection it should apply to; x of an
+ * earlier selection is not recomputed.  The kinematic fields read the frame
+ * the handle holds WHEN THEY ARE EVALUATED, not the one a selection was made
+ * with: changing the frame between a selection and a kinematic call mixes
+ * two frames without an error, so keep it unchanged across the two (after
+ * pbx_profile_set_x there is no selection: set the frame any time before
+ * the kinematic call).  With a frame set, float32 positions
+ * in pbx_profile_select_typed and the distributed entry
+ * pbx_profile_radial_equaln_comm are a PBX_ERR_VALUE, and so are unknown
+ * flag bits. */
+#define PBX_FRAME_POS 1
+#define PBX_FRAME_VEL 2
+#define PBX_FRAME_ROT 4
+int pbx_profile_set_frame(void *handle, int flags, const double *frame);
 /* One equaln radial-profile pass after pbx_profile_select with a single host
  * round trip (bins.py:720-746 edges, :346-395 assignment, the CSR when
  * build_csr, and per-bin sums of n_stats <= 16 requests (f_src / w_src in
@@ -586,6 +618,20 @@ int pbx_property_moments(const double *pos, const double *vel, const double *mas
                          int on_device, int use_sphere, const double *sphere,
                          const int64_t *fam, int nfam, uint32_t groups, int64_t *n_kept,
                          double *h_sums);
+/* The same pass in a frame (flags / frame[15] as in pbx_profile_set_frame;
+ * flags == 0 or frame == NULL: exactly pbx_property_moments).  Positions and
+ * velocities are taken to the frame first; the Sphere test (its centre in
+ * frame coordinates) and every term are then evaluated from x', v' as above.
+ * pos is read when there is a sphere or a position group, as before; vel for
+ * a velocity group.  The frame constants are kernel arguments, and the
+ * frame-less instantiations of the kernel are the ones pbx_property_moments
+ * launches.  The summation order depends on the particle count alone, so the
+ * sums equal, bit for bit, those of pbx_property_moments on arrays rewritten
+ * with the restatement above. */
+int pbx_property_moments_frame(const double *pos, const double *vel, const double *mass, int64_t n,
+                               int on_device, int use_sphere, const double *sphere,
+                               const int64_t *fam, int nfam, uint32_t groups, int flags,
+                               const double *frame, int64_t *n_kept, double *h_sums);
 /* Shrinking-sphere centre of the particles in the family ranges (all when
  * nfam = 0) — the centre CenPos("ssc") asks pynbody for
  * (properties/generic.py:54-55).  The particles are staged once (or

@@ -27,6 +27,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "frame.h"
 #include "prims.h"
 
 
@@ -54,6 +55,7 @@ struct SelectParams {
   double cx, cy, cz, r2max;
   int64_t fam_lo[MAX_FAM];
   int64_t fam_hi[MAX_FAM];
+  FrameHalf fr;  // the handle's frame for positions (pbx_profile_set_frame); float64 only
 };
 
 // family membership of particle i (contiguous slices; no slices = all)
@@ -75,6 +77,9 @@ template <typename T>
 __device__ __forceinline__ bool select_xyz(T px, T py, T pz, const SelectParams &p, double &x) {
 #pragma clang fp contract(off)
   if constexpr (std::is_same<T, double>::value) {
+    // the frame first (uniform: a scalar branch); everything below then reads
+    // the frame's coordinates, the origin shortcut included
+    if (__builtin_expect(p.fr.shift | p.fr.rot, 0)) frame_apply(p.fr, px, py, pz);
     // a Sphere at the origin: dx = x - 0.0 is x exactly (NaN and -0.0
     // included), so ((dx*dx + dy*dy) + dz*dz) is r^2 itself — one sum of
     // squares for both the test and r
@@ -4341,21 +4346,39 @@ __global__ void __launch_bounds__(MONO_BT) radial_mono(MonoArgs a) {
 
 // ----------------------------------------------------------------- moments
 // LDS: accumulators in LDS (nb <= LDS_MOM_BINS), one slab row per block;
-// else straight to global_acc.  Templated so the LDS path indexes the
+// else straight to global_acc.  In LDS no two waves ever add into the same
+// accumulator at once: each wave has its own copy of the accumulators while
+// four copies fit (lds_copies; they are added in wave order at the end),
+// else the waves of a block add into the one copy in turn (wave 0, then 1,
+// ...).  A wave's own adds reach an accumulator in
+// program and lane order, so with the fixed slab reduction the sums are the
+// same bits from call to call — a profile built twice, or once in a frame and
+// once on rewritten arrays, gives identical statistics.  (All waves at once,
+// the order in which their adds met was the scheduler's.)  This rests on two
+// assumptions, neither documented by the vendor: that the lanes of ONE
+// ds_add_f64 that hit the same address are always resolved in the same order,
+// and that a wave is 64 lanes (TPB / 64 turns; gfx950 runs these kernels in
+// wave64).  Observed to hold; if the first did not, the last bits of a
+// statistic would again move between calls, within the usual bound.  Templated so the LDS path indexes the
 // __shared__ array itself (ds_add_f64): through a pointer that may be either,
 // every atomic would be a flat atomic.
 template <int WMODE, bool LDS>  // WMODE 0: no weights, 1: weights
 __global__ void __launch_bounds__(TPB)
     moments_kernel(const uint32_t *__restrict__ bins, const double *__restrict__ f,
                    const double *__restrict__ wt, int64_t n, int nb, uint32_t cols,
-                   double *__restrict__ slab, double *__restrict__ global_acc) {
+                   int copies, double *__restrict__ slab, double *__restrict__ global_acc) {
   extern __shared__ double acc_lds[];
+  // copies == TPB / 64: every wave owns a copy of the accumulators (no wave
+  // meets another's adds, no turns needed); copies == 1: one shared copy,
+  // the waves take turns
+  const int wave = threadIdx.x >> 6, wlen = nb * NMOM;
+  const int woff = (LDS && copies > 1) ? wave * wlen : 0;
   if (LDS) {
-    for (int k = threadIdx.x; k < nb * NMOM; k += TPB) acc_lds[k] = 0.0;
+    for (int k = threadIdx.x; k < wlen * copies; k += TPB) acc_lds[k] = 0.0;
     __syncthreads();
   }
   auto add = [&](int64_t idx, double v) {
-    if (LDS) atomicAdd(&acc_lds[idx], v);
+    if (LDS) atomicAdd(&acc_lds[woff + idx], v);
     else atomicAdd(&global_acc[idx], v);
   };
   // grid-stride over tiles: at most gridDim.x slabs to reduce afterwards
@@ -4370,27 +4393,38 @@ __global__ void __launch_bounds__(TPB)
       fv[k] = ok ? f[i] : 0.0;
       wv[k] = (WMODE && ok) ? wt[i] : 1.0;
     }
+    // (the loop bounds are the block's: every thread meets every barrier)
+    const int nturn = (LDS && copies == 1) ? TPB / 64 : 1;
+    for (int turn = 0; turn < nturn; ++turn) {
+      if (nturn == 1 || wave == turn) {
 #pragma unroll
-    for (int k = 0; k < IPT; ++k) {
-      if (bv[k] >= (uint32_t)nb) continue;
-      const double v = fv[k], a = __builtin_fabs(v), ww = wv[k];
-      const int64_t t = (int64_t)bv[k] * NMOM;
-      // only the requested columns (cols is uniform: scalar branches)
-      if (WMODE) {
-        if (cols & 1u) add(t + 0, ww);
-        if (cols & 2u) add(t + 1, v * ww);
-        if (cols & 4u) add(t + 2, (v * v) * ww);
-        if (cols & 32u) add(t + 5, a * ww);
+        for (int k = 0; k < IPT; ++k) {
+          if (bv[k] >= (uint32_t)nb) continue;
+          const double v = fv[k], a = __builtin_fabs(v), ww = wv[k];
+          const int64_t t = (int64_t)bv[k] * NMOM;
+          // only the requested columns (cols is uniform: scalar branches)
+          if (WMODE) {
+            if (cols & 1u) add(t + 0, ww);
+            if (cols & 2u) add(t + 1, v * ww);
+            if (cols & 4u) add(t + 2, (v * v) * ww);
+            if (cols & 32u) add(t + 5, a * ww);
+          }
+          if (cols & 8u) add(t + 3, v);
+          if (cols & 16u) add(t + 4, v * v);
+          if (cols & 64u) add(t + 6, a);
+        }
       }
-      if (cols & 8u) add(t + 3, v);
-      if (cols & 16u) add(t + 4, v * v);
-      if (cols & 64u) add(t + 6, a);
+      if (nturn > 1) __syncthreads();
     }
   }
   if (LDS) {
     __syncthreads();
-    double *dst = slab + (int64_t)blockIdx.x * nb * NMOM;
-    for (int k = threadIdx.x; k < nb * NMOM; k += TPB) dst[k] = acc_lds[k];
+    double *dst = slab + (int64_t)blockIdx.x * wlen;
+    for (int k = threadIdx.x; k < wlen; k += TPB) {
+      double t = acc_lds[k];  // the waves' copies in wave order
+      for (int c = 1; c < copies; ++c) t = t + acc_lds[c * wlen + k];
+      dst[k] = t;
+    }
   }
 }
 
@@ -4471,13 +4505,17 @@ __device__ __forceinline__ double kin_pick(const double f[KIN_NF], int code) {
 // one field in selection order (idx NULL: identity, a set_x handle)
 __global__ void __launch_bounds__(TPB)
     kin_field_kernel(const int32_t *__restrict__ idx, const double *__restrict__ pos,
-                     const double *__restrict__ vel, int64_t n, int code,
+                     const double *__restrict__ vel, int64_t n, int code, Frame fr, int framed,
                      double *__restrict__ out) {
   const int64_t t = (int64_t)blockIdx.x * TPB + threadIdx.x;
   if (t >= n) return;
   const int64_t i = idx ? (int64_t)idx[t] : t;
-  const double p[3] = {pos[3 * i], pos[3 * i + 1], pos[3 * i + 2]};
-  const double v[3] = {vel[3 * i], vel[3 * i + 1], vel[3 * i + 2]};
+  double p[3] = {pos[3 * i], pos[3 * i + 1], pos[3 * i + 2]};
+  double v[3] = {vel[3 * i], vel[3 * i + 1], vel[3 * i + 2]};
+  if (framed) {
+    frame_apply(fr.pos, p[0], p[1], p[2]);
+    frame_apply(fr.vel, v[0], v[1], v[2]);
+  }
   double f[KIN_NF];
   kin_fields(p, v, 1u << code, f);
   out[t] = kin_pick(f, code);
@@ -4498,11 +4536,14 @@ struct KinPlan {
 __global__ void __launch_bounds__(TPB)
     kin_moments_kernel(const uint32_t *__restrict__ bins, const int32_t *__restrict__ idx,
                        const double *__restrict__ wt, const double *__restrict__ pos,
-                       const double *__restrict__ vel, int64_t n, int nb, KinPlan plan,
-                       double *__restrict__ slab) {
+                       const double *__restrict__ vel, int64_t n, int nb, KinPlan plan, Frame fr,
+                       int framed, int copies, double *__restrict__ slab) {
   extern __shared__ double acc_lds[];
   const int len = nb * plan.nslots;
-  for (int k = threadIdx.x; k < len; k += TPB) acc_lds[k] = 0.0;
+  // (copies: as in moments_kernel — a copy per wave, or one copy and turns)
+  const int wave = threadIdx.x >> 6, woff = copies > 1 ? wave * len : 0;
+  const int nturn = copies == 1 ? TPB / 64 : 1;
+  for (int k = threadIdx.x; k < len * copies; k += TPB) acc_lds[k] = 0.0;
   __syncthreads();
   for (int64_t base = (int64_t)blockIdx.x * KIN_TILE; base < n;
        base += (int64_t)gridDim.x * KIN_TILE) {
@@ -4521,31 +4562,52 @@ __global__ void __launch_bounds__(TPB)
         v[k][c] = ok ? vel[3 * i + c] : 0.0;
       }
     }
+    // the fields of the tile's elements, every wave at once (the frame, the
+    // square roots and the divisions are outside the turns below)
+    double fk[KIN_IPT][KIN_NF];
 #pragma unroll
     for (int k = 0; k < KIN_IPT; ++k) {
       if (bv[k] >= (uint32_t)nb) continue;
-      double f[KIN_NF];
-      kin_fields(p[k], v[k], plan.need, f);
-      const double ww = wv[k];
-      double *a = acc_lds + (int)bv[k] * plan.nslots;
-      if (plan.wslot >= 0) atomicAdd(&a[plan.wslot], ww);
-#pragma unroll
-      for (int j = 0; j < KIN_NF; ++j) {
-        if (j >= plan.nf) break;
-        const double val = kin_pick(f, plan.code[j]), ab = __builtin_fabs(val);
-        const int8_t *s = plan.slot[j];
-        if (s[1] >= 0) atomicAdd(&a[s[1]], val * ww);
-        if (s[2] >= 0) atomicAdd(&a[s[2]], (val * val) * ww);
-        if (s[3] >= 0) atomicAdd(&a[s[3]], val);
-        if (s[4] >= 0) atomicAdd(&a[s[4]], val * val);
-        if (s[5] >= 0) atomicAdd(&a[s[5]], ab * ww);
-        if (s[6] >= 0) atomicAdd(&a[s[6]], ab);
+      if (framed) {  // (uniform)
+        frame_apply(fr.pos, p[k][0], p[k][1], p[k][2]);
+        frame_apply(fr.vel, v[k][0], v[k][1], v[k][2]);
       }
+      kin_fields(p[k], v[k], plan.need, fk[k]);
+    }
+    // only the LDS adds take turns, wave by wave as in moments_kernel: the
+    // same bits from call to call
+    for (int turn = 0; turn < nturn; ++turn) {
+      if (nturn == 1 || wave == turn) {
+#pragma unroll
+        for (int k = 0; k < KIN_IPT; ++k) {
+          if (bv[k] >= (uint32_t)nb) continue;
+          const double ww = wv[k];
+          double *a = acc_lds + woff + (int)bv[k] * plan.nslots;
+          if (plan.wslot >= 0) atomicAdd(&a[plan.wslot], ww);
+#pragma unroll
+          for (int j = 0; j < KIN_NF; ++j) {
+            if (j >= plan.nf) break;
+            const double val = kin_pick(fk[k], plan.code[j]), ab = __builtin_fabs(val);
+            const int8_t *s = plan.slot[j];
+            if (s[1] >= 0) atomicAdd(&a[s[1]], val * ww);
+            if (s[2] >= 0) atomicAdd(&a[s[2]], (val * val) * ww);
+            if (s[3] >= 0) atomicAdd(&a[s[3]], val);
+            if (s[4] >= 0) atomicAdd(&a[s[4]], val * val);
+            if (s[5] >= 0) atomicAdd(&a[s[5]], ab * ww);
+            if (s[6] >= 0) atomicAdd(&a[s[6]], ab);
+          }
+        }
+      }
+      if (nturn > 1) __syncthreads();
     }
   }
   __syncthreads();
   double *dst = slab + (int64_t)blockIdx.x * len;
-  for (int k = threadIdx.x; k < len; k += TPB) dst[k] = acc_lds[k];
+  for (int k = threadIdx.x; k < len; k += TPB) {
+    double t = acc_lds[k];  // the waves' copies in wave order
+    for (int c = 1; c < copies; ++c) t = t + acc_lds[c * len + k];
+    dst[k] = t;
+  }
 }
 
 // ---------------------------------------------- per-bin order statistics
@@ -4842,6 +4904,9 @@ struct Profile {
   int64_t src_n = 0;  // length of the arrays the selection was made from
   const double *kin_pos = nullptr, *kin_vel = nullptr;
   Buf kpos, kvel;
+  // pbx_profile_set_frame: how the handle reads particles (sticky across
+  // selections; every flag off = no frame)
+  Frame frame{};
   bool posst_sel = false;  // posst holds this selection's positions (a lazy selection of host arrays)
 };
 
@@ -5197,6 +5262,9 @@ static SelPrep select_prep(Profile &P, hipStream_t st, const SelectReq &q, bool 
   const int64_t lo = fsp.lo, hi = fsp.hi, span = hi - lo;
   sp.base = lo;
   if (lazy && (pos_f32 || mass_f32)) fail(PBX_ERR_VALUE, "the lazy selection takes float64 arrays");
+  if (pos_f32 && P.frame.any())
+    fail(PBX_ERR_VALUE, "a frame is set on this handle: float32 positions are not supported");
+  sp.fr = P.frame.pos;
   sp.mass_f32 = mass_f32;
   const size_t ps = pos_f32 ? sizeof(float) : sizeof(double);
   const size_t ms = mass_f32 ? sizeof(float) : sizeof(double);
@@ -5466,7 +5534,7 @@ static void kin_field_device(Profile &P, hipStream_t st, int code, double *out) 
   if (!n) return;
   const int32_t *idx = kin_idx(P, st);
   hipLaunchKernelGGL(kin_field_kernel, dim3(ceil_div(n, TPB)), dim3(TPB), 0, st, idx, P.kin_pos,
-                     P.kin_vel, n, code, out);
+                     P.kin_vel, n, code, P.frame, (int)P.frame.any(), out);
   PBX_HIP(hipGetLastError());
 }
 
@@ -5511,6 +5579,15 @@ static const double *resolve_src(Profile &P, hipStream_t st, int which, const do
 }
 
 // per-bin sums of the requested columns into acc (nb x NMOM doubles, device)
+// LDS copies of `len` per-bin accumulators in the sum kernels: one per wave
+// while the four fit in the footprint the kernels already had at their
+// largest (LDS_MOM_BINS bins x 7 sums; 128 bins x 7 sums x 4 is 28 KB), else
+// one shared copy whose adds the waves make in turn
+constexpr size_t LDS_COPY_BYTES = sizeof(double) * LDS_MOM_BINS * NMOM;
+static int lds_copies(int64_t len) {
+  return sizeof(double) * (size_t)len * (TPB / 64) <= LDS_COPY_BYTES ? TPB / 64 : 1;
+}
+
 static void moments_device(Profile &P, hipStream_t st, int f_src, const double *h_f, Buf &fstage,
                            int w_src, const double *h_w, Buf &wstage, uint32_t cols,
                            double *acc) {
@@ -5528,11 +5605,12 @@ static void moments_device(Profile &P, hipStream_t st, int f_src, const double *
     uint32_t nt = std::min<uint32_t>(ntiles_of(n), 1024u);
     const bool in_lds = nb <= LDS_MOM_BINS;
     double *slab = in_lds ? (double *)P.slab.get(sizeof(double) * (size_t)nt * len) : nullptr;
-    size_t lds = in_lds ? sizeof(double) * (size_t)len : 0;
+    const int copies = lds_copies(len);
+    size_t lds = in_lds ? sizeof(double) * (size_t)len * copies : 0;
     auto launch = [&](auto wm, auto lds_t) {
       hipLaunchKernelGGL((moments_kernel<decltype(wm)::value, decltype(lds_t)::value>), dim3(nt),
                          dim3(TPB), lds, st, (const uint32_t *)P.bins.p, f, w, n, (int)nb, cols,
-                         slab, acc);
+                         copies, slab, acc);
     };
     using W1 = std::integral_constant<int, 1>;
     using W0 = std::integral_constant<int, 0>;
@@ -6885,6 +6963,17 @@ int pbx_profile_set_kinematics(void *handle, const double *pos, const double *ve
   });
 }
 
+// The frame the handle reads particles in (frame.h): honoured by the next
+// selections (select_prep -> select_xyz) and by the kinematic fields.  Sticky;
+// flags == 0 or a NULL frame clears it.
+int pbx_profile_set_frame(void *handle, int flags, const double *frame) {
+  return with_profile(handle, [&](Profile &P, Device &d, hipStream_t st) {
+    if (flags & ~(PBX_FRAME_POS | PBX_FRAME_VEL | PBX_FRAME_ROT))
+      fail(PBX_ERR_VALUE, "flags must be a mask of PBX_FRAME_* bits (got 0x%x)", flags);
+    P.frame = frame_of(flags, frame);
+  });
+}
+
 // Field `code` of the kept particles, in selection order, to the host
 // (P.n doubles): the per-particle read behind sub["vr"].
 int pbx_profile_kinematic_field(void *handle, int code, double *h_out) {
@@ -6950,9 +7039,11 @@ int pbx_profile_kinematic_moments(void *handle, int n_fields, const int *codes, 
     double *slab = (double *)P.slab.get(sizeof(double) * (size_t)nt * plen);
     double *acc = (double *)P.acc.get(sizeof(double) * (size_t)plen);
     double *part = (double *)P.slabp.get(sizeof(double) * (size_t)SLAB_G * plen);
-    hipLaunchKernelGGL(kin_moments_kernel, dim3(nt), dim3(TPB), sizeof(double) * (size_t)plen, st,
+    const int copies = lds_copies(plen);
+    hipLaunchKernelGGL(kin_moments_kernel, dim3(nt), dim3(TPB),
+                       sizeof(double) * (size_t)plen * copies, st,
                        (const uint32_t *)P.bins.p, idx, w, P.kin_pos, P.kin_vel, n, (int)nb, plan,
-                       slab);
+                       P.frame, (int)P.frame.any(), copies, slab);
     PBX_HIP(hipGetLastError());
     hipLaunchKernelGGL(reduce_slab_part, dim3(ceil_div(plen, TPB), SLAB_G), dim3(TPB), 0, st, slab,
                        (int64_t)nt, plen, part);
@@ -7078,6 +7169,8 @@ static int radial_equaln_entry(void *comm, void *handle, const SelectReq &q, int
   return guard([&] {
     Profile &P = as_profile(handle);
     const CommRanks cr = comm ? comm_ranks(comm) : CommRanks{1, 0};
+    if (comm && P.frame.any())
+      fail(PBX_ERR_VALUE, "a frame is set on this handle: the distributed profile takes none");
     check_stat_args(nbins, stats);
     Device &d = current_device();
     std::unique_lock<std::mutex> lk(d.mu);  // (released inside comm_allreduce's host wait)

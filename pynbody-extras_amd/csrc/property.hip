@@ -20,6 +20,7 @@
 #include <cmath>
 #include <cstring>
 
+#include "frame.h"
 #include "pbx_common.h"
 
 namespace pbx {
@@ -75,11 +76,14 @@ __device__ __forceinline__ bool prop_in_sphere(double x, double y, double z, con
 
 // One pass over the particles [base, base + span).  POS / VEL: the pass
 // reads positions / velocities at all (a sphere or a position group; a
-// velocity group).  part: one row of NS sums per block; cnt: its count.
-template <bool POS, bool VEL>
+// velocity group).  FRAME: what was read is taken to the frame `fr` before
+// the sphere test and the terms (frame.h); without it fr is not looked at and
+// the pass is the frame-less one.  part: one row of NS sums per block; cnt:
+// its count.
+template <bool POS, bool VEL, bool FRAME>
 __global__ void __launch_bounds__(PROP_TPB)
     property_moments(const double *__restrict__ pos, const double *__restrict__ vel,
-                     const double *__restrict__ mass, PropParams p, uint32_t groups,
+                     const double *__restrict__ mass, PropParams p, Frame fr, uint32_t groups,
                      double *__restrict__ part, long long *__restrict__ cnt) {
 #pragma clang fp contract(off)
   __shared__ double ws[PROP_NW][NS];
@@ -112,6 +116,13 @@ __global__ void __launch_bounds__(PROP_TPB)
         vx[k] = q[0];
         vy[k] = q[1];
         vz[k] = q[2];
+      }
+    }
+    if constexpr (FRAME) {
+#pragma unroll
+      for (int k = 0; k < PROP_ITEMS; ++k) {
+        if constexpr (POS) frame_apply(fr.pos, x[k], y[k], z[k]);
+        if constexpr (VEL) frame_apply(fr.vel, vx[k], vy[k], vz[k]);
       }
     }
     if (p.use_sphere) {
@@ -265,6 +276,7 @@ static void check_common(int64_t n, const int64_t *fam, int nfam) {
 struct Staged {
   PropParams p{};
   const double *pos = nullptr, *vel = nullptr, *mass = nullptr;
+  Frame fr{};  // (all flags off: the frame-less kernels)
 };
 
 static const double *stage(Device &d, hipStream_t st, const double *a, int width, int64_t lo,
@@ -311,13 +323,20 @@ static void run_pass(Device &d, hipStream_t st, const Staged &s, uint32_t groups
   const bool use_pos = s.p.use_sphere || (groups & POS_GROUPS);
   const bool use_vel = (groups & VEL_GROUPS) != 0;
   auto launch = [&](auto kern) {
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(PROP_TPB), 0, st, s.pos, s.vel, s.mass, s.p, groups,
-                       part, cnt);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(PROP_TPB), 0, st, s.pos, s.vel, s.mass, s.p, s.fr,
+                       groups, part, cnt);
   };
-  if (use_pos && use_vel) launch(property_moments<true, true>);
-  else if (use_pos) launch(property_moments<true, false>);
-  else if (use_vel) launch(property_moments<false, true>);
-  else launch(property_moments<false, false>);
+  // (a frame half whose array the pass does not read changes nothing)
+  const bool framed = (use_pos && (s.fr.pos.shift || s.fr.pos.rot)) ||
+                      (use_vel && (s.fr.vel.shift || s.fr.vel.rot));
+  if (framed) {
+    if (use_pos && use_vel) launch(property_moments<true, true, true>);
+    else if (use_pos) launch(property_moments<true, false, true>);
+    else launch(property_moments<false, true, true>);
+  } else if (use_pos && use_vel) launch(property_moments<true, true, false>);
+  else if (use_pos) launch(property_moments<true, false, false>);
+  else if (use_vel) launch(property_moments<false, true, false>);
+  else launch(property_moments<false, false, false>);
   PBX_HIP(hipGetLastError());
   hipLaunchKernelGGL(property_reduce, dim3(1), dim3(PROP_RG * PROP_NOUT), 0, st, part, cnt, grid,
                      out);
@@ -337,10 +356,13 @@ using namespace pbx::prop;
 
 extern "C" {
 
-int pbx_property_moments(const double *pos, const double *vel, const double *mass, int64_t n,
-                         int on_device, int use_sphere, const double *sphere, const int64_t *fam,
-                         int nfam, uint32_t groups, int64_t *n_kept, double *h_sums) {
+int pbx_property_moments_frame(const double *pos, const double *vel, const double *mass, int64_t n,
+                               int on_device, int use_sphere, const double *sphere,
+                               const int64_t *fam, int nfam, uint32_t groups, int flags,
+                               const double *frame, int64_t *n_kept, double *h_sums) {
   return guard([&] {
+    if (flags & ~(PBX_FRAME_POS | PBX_FRAME_VEL | PBX_FRAME_ROT))
+      fail(PBX_ERR_VALUE, "flags must be a mask of PBX_FRAME_* bits (got 0x%x)", flags);
     if (!n_kept || !h_sums) fail(PBX_ERR_VALUE, "null output");
     check_common(n, fam, nfam);
     if (groups == 0 || (groups & ~ALL_GROUPS))
@@ -365,8 +387,16 @@ int pbx_property_moments(const double *pos, const double *vel, const double *mas
       s.p.cz = sphere[2];
       s.p.r2max = sphere[3];
     }
+    s.fr = frame_of(flags, frame);
     run_pass(d, st, s, groups, n_kept, h_sums);
   });
+}
+
+int pbx_property_moments(const double *pos, const double *vel, const double *mass, int64_t n,
+                         int on_device, int use_sphere, const double *sphere, const int64_t *fam,
+                         int nfam, uint32_t groups, int64_t *n_kept, double *h_sums) {
+  return pbx_property_moments_frame(pos, vel, mass, n, on_device, use_sphere, sphere, fam, nfam,
+                                    groups, 0, nullptr, n_kept, h_sums);
 }
 
 int pbx_property_shrink_center(const double *pos, const double *mass, int64_t n, int on_device,

@@ -35,6 +35,11 @@ WANT_ACC = 2
 KINEMATIC_FIELDS = ("vr", "vtheta", "vphi", "vrxy", "v2", "vt")
 SRC_KIN = 16
 
+# frame flags (pbx.h PBX_FRAME_*): position shift, velocity shift, rotation
+FRAME_POS = 1
+FRAME_VEL = 2
+FRAME_ROT = 4
+
 _LIB_NAME = "libpbx.so"
 _lib: ctypes.CDLL | None = None
 
@@ -164,6 +169,9 @@ _SIGNATURES: dict[str, tuple] = {
     "pbx_profile_contain": (c_int, [c_void_p, c_int, c_void_p, c_int, _dp, _dp, _dp]),
     "pbx_property_moments": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, _dp,
                                      _i64p, c_int, c_uint32, _i64p, _dp]),
+    "pbx_profile_set_frame": (c_int, [c_void_p, c_int, _dp]),
+    "pbx_property_moments_frame": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int,
+                                           _dp, _i64p, c_int, c_uint32, c_int, _dp, _i64p, _dp]),
     "pbx_property_shrink_center": (c_int, [c_void_p, c_void_p, c_int64, c_int, _i64p, c_int,
                                            c_double, c_double, c_int64, _dp, _i64p, _i64p]),
     "pbx_comm_unique_id_size": (c_int, []),

@@ -8,9 +8,10 @@ through, with the same names and semantics:
 * ``CalculatorBase.__call__(sim, options=None, **overrides)`` -> value,
   ``run(...)`` -> :class:`Result`, ``filter(f)`` / ``with_filter(f)``
   (core/calculate/base.py:559-704),
-* ``BoundCalculator``: evaluates its filter scope, then the wrapped
-  calculator on ``source_sim[mask]`` (base.py:874-1008,
-  context.py:610-646),
+* ``BoundCalculator``: evaluates its transform, then its filter scope in
+  the transformed frame, then the wrapped calculator on ``source_sim[mask]``
+  (base.py:874-1008, context.py:610-646); ``transform(t, revert=True)`` /
+  ``with_transformation`` (template.py:39-58),
 * ``FilterBase`` with ``&``, ``|``, ``~`` composition (filters.py:124-313),
 * ``RunOptions`` / ``ExecutionContext.phase`` / dynamic parameters
   (context.py:503-533, base.py:422),
@@ -23,13 +24,17 @@ through, with the same names and semantics:
 MI355X addition: a calculator may implement ``execute_fused(ctx, input,
 filt)``; a bound calculator offers it its filter first, so a radial profile
 behind a Sphere / FamilyFilter scope runs mask + r + binning as one device
-pipeline instead of materialising the masked snapshot on the host.
+pipeline instead of materialising the masked snapshot on the host.  A
+transform scope does not rewrite ``pos`` / ``vel``: it resolves to a frame
+(pynbodyext.frame) that rides along in those device passes, and the
+snapshot an evaluation sees is a :class:`~pynbodyext.frame.FrameView`.
 """
 from __future__ import annotations
 
 import copy
 import dataclasses
 import operator
+import threading
 import time
 from contextlib import contextmanager
 from dataclasses import dataclass, field
@@ -43,8 +48,17 @@ __all__ = ["RunOptions", "Result", "NodeInput", "ExecutionContext", "CalculatorB
            "OpProperty"]
 
 
+BACKENDS = ("mi355x", "host")
+
+
 @dataclass
 class RunOptions:
+    """backend: "mi355x" (default) lets a calculator take its device route;
+    "host" keeps every calculator on the reference's numpy ``calculate`` /
+    mask (profiles are built on the device either way).  A calculator
+    evaluated from inside a run — a Sphere's radius given as a calculator —
+    inherits the options of that run unless it is given its own."""
+
     cache: bool = True
     progress: Any = False
     perf_time: bool = False
@@ -74,6 +88,11 @@ class NodeInput:
         self._active = None
 
     @property
+    def frame(self):
+        """The frame ``source_sim`` is seen in (a FrameView's), or None."""
+        return getattr(self.source_sim, "_frame", None)
+
+    @property
     def active_sim(self):
         if self.mask is None:
             return self.source_sim
@@ -89,10 +108,19 @@ class NodeInput:
         return NodeInput(self.source_sim, mask, filt)
 
 
+_active = threading.local()  # .stack: the ExecutionContexts of the runs in progress
+
+
 class ExecutionContext:
     def __init__(self, options: RunOptions):
+        if options.backend not in BACKENDS:
+            raise ValueError(f"unknown backend {options.backend!r}; expected one of {list(BACKENDS)}")
         self.options = options
         self.perf: dict[str, float] = {}
+
+    @property
+    def on_host(self) -> bool:
+        return self.options.backend == "host"
 
     @contextmanager
     def phase(self, node, name: str):
@@ -119,7 +147,10 @@ def resolve_value_in_units(value, sim, field_name: str | None):
     from ._pyn import units as _units
 
     if isinstance(value, str) or isinstance(value, getattr(_units, "UnitBase", ())):
-        target = sim[field_name].units if field_name else None
+        # (the unit table, not the array: a frame view derives its pos on demand)
+        unit_of = getattr(sim, "_unit_of", None)
+        target = None if not field_name else \
+            unit_of(field_name) if unit_of is not None else sim[field_name].units
         u = _units.Unit(value) if isinstance(value, str) else value
         return float(u.ratio(target)) if target is not None else float(u.ratio(_units.NoUnit))
     return value
@@ -139,14 +170,26 @@ class CalculatorBase:
         return value
 
     def run(self, sim, options: RunOptions | None = None, **overrides) -> Result:
-        opts = copy.copy(options) if options is not None else copy.copy(self.default_options)
+        stack = _active.__dict__.setdefault("stack", [])
+        if options is not None:
+            opts = copy.copy(options)
+        else:  # (a run started from inside another inherits its options)
+            opts = copy.copy(stack[-1].options if stack else self.default_options)
         for k, v in overrides.items():
             if v is not None:
                 if not hasattr(opts, k):
                     raise TypeError(f"unknown run option {k!r}")
                 setattr(opts, k, v)
         ctx = ExecutionContext(opts)
-        value = self.public_value(ctx.raw_value(self, NodeInput(sim)))
+        stack.append(ctx)
+        try:
+            value = self.public_value(ctx.raw_value(self, NodeInput(sim)))
+        finally:
+            stack.pop()
+            if stack:  # (its phases count in the run it was started from, too)
+                outer = stack[-1].perf
+                for k, v in ctx.perf.items():
+                    outer[k] = outer.get(k, 0.0) + v
         return Result(value, ctx.perf)
 
     def __call__(self, sim, options: RunOptions | None = None, *, cache=None, progress=None,
@@ -167,6 +210,16 @@ class CalculatorBase:
     def filter(self, filt: "FilterBase") -> "BoundCalculator":
         return self.with_filter(filt)
 
+    def with_transformation(self, transform, *, revert: bool = True) -> "BoundCalculator":
+        """This calculator evaluated in the frame ``transform`` (a
+        pynbodyext.transforms node or chain) leads to.  revert=True leaves
+        the snapshot as it was (it is never touched); revert=False rewrites
+        its ``pos`` / ``vel`` into that frame once the value is computed."""
+        return BoundCalculator(self, None, transform, revert)
+
+    def transform(self, transform, *, revert: bool = True) -> "BoundCalculator":
+        return self.with_transformation(transform, revert=revert)
+
     # -- dynamic parameters ------------------------------------------------------
     def resolve_dynamic_params(self, ctx: ExecutionContext, input: NodeInput) -> dict:
         out = {}
@@ -184,22 +237,85 @@ class CalculatorBase:
         return (type(self).__name__, id(self))
 
 
-class BoundCalculator(CalculatorBase):
-    """A calculator evaluated on the subset selected by a filter scope."""
+class _Arithmetic:
+    """Host-side ``+ - * /`` and unary ``-`` into OpProperty, shared by
+    PropertyBase and BoundCalculator: a scoped property keeps them, as in
+    ``0.5 * ParamContain("r").filter(f)``."""
 
-    def __init__(self, base: CalculatorBase, filt: "FilterBase"):
+    # -- host-side arithmetic --------------------------------------------------
+    @classmethod
+    def as_property(cls, other) -> "PropertyBase":
+        return other if isinstance(other, CalculatorBase) else ConstantProperty(other)
+
+    def __add__(self, other):
+        return OpProperty("add", self, self.as_property(other))
+
+    def __radd__(self, other):
+        return OpProperty("add", self.as_property(other), self)
+
+    def __sub__(self, other):
+        return OpProperty("sub", self, self.as_property(other))
+
+    def __rsub__(self, other):
+        return OpProperty("sub", self.as_property(other), self)
+
+    def __mul__(self, other):
+        return OpProperty("mul", self, self.as_property(other))
+
+    def __rmul__(self, other):
+        return OpProperty("mul", self.as_property(other), self)
+
+    def __truediv__(self, other):
+        return OpProperty("truediv", self, self.as_property(other))
+
+    def __rtruediv__(self, other):
+        return OpProperty("truediv", self.as_property(other), self)
+
+    def __neg__(self):
+        return OpProperty("neg", self)
+
+
+class BoundCalculator(_Arithmetic, CalculatorBase):
+    """A calculator evaluated in a transform's frame (if any) on the subset
+    selected by a filter scope (if any): the transform first, then the
+    filter in the transformed frame, then the calculator."""
+
+    def __init__(self, base: CalculatorBase, filt: "FilterBase | None" = None, transform=None,
+                 revert: bool = True):
         self.base = base
         self.pre_filter = filt
+        self.pre_transform = transform
+        self.revert = bool(revert)
 
     def with_filter(self, filt: "FilterBase") -> "BoundCalculator":
-        return BoundCalculator(self.base, self.pre_filter & filt)
+        f = filt if self.pre_filter is None else self.pre_filter & filt
+        return BoundCalculator(self.base, f, self.pre_transform, self.revert)
+
+    def with_transformation(self, transform, *, revert: bool = True) -> "BoundCalculator":
+        t = transform if self.pre_transform is None else self.pre_transform.then(transform)
+        return BoundCalculator(self.base, self.pre_filter, t, self.revert and revert)
 
     def public_value(self, value):
         return self.base.public_value(value)
 
     def execute(self, ctx: ExecutionContext, input: NodeInput):
+        if self.pre_transform is None:
+            return self._execute_scoped(ctx, input)
+        sim = input.active_sim
+        with ctx.phase(self, "transform"):
+            framed = self.pre_transform.framed_sim(ctx, sim)
+        value = self._execute_scoped(ctx, NodeInput(framed))
+        if not self.revert:
+            with ctx.phase(self, "rewrite"):
+                _rewrite_in_place(sim, framed)
+        return value
+
+    def _execute_scoped(self, ctx: ExecutionContext, input: NodeInput):
+        if self.pre_filter is None:
+            with ctx.phase(self, "calculate"):
+                return ctx.raw_value(self.base, input)
         fused = getattr(self.base, "execute_fused", None)
-        if fused is not None and input.mask is None:
+        if fused is not None and input.mask is None and not ctx.on_host:
             with ctx.phase(self, "fused"):
                 res = fused(ctx, input, self.pre_filter)
             if res is not NotImplemented:
@@ -209,6 +325,24 @@ class BoundCalculator(CalculatorBase):
             work = input.with_selection(mask, self.pre_filter)
         with ctx.phase(self, "calculate"):
             return ctx.raw_value(self.base, work)
+
+
+def _rewrite_in_place(sim, framed) -> None:
+    """revert=False: the particles of ``sim`` take the positions and
+    velocities ``framed`` (the same particles in the transform's frame)
+    shows, written into the root snapshot's own arrays."""
+    root = sim.ancestor
+    index = getattr(sim, "_root_index", None)
+    rows = slice(None) if index is None else index
+    stored = getattr(root, "_arrays", None)
+    for key in ("pos", "vel"):
+        if stored is None:  # (a pynbody snapshot: its arrays write through)
+            if key in root.keys():
+                root[key][rows] = np.asarray(framed[key])
+        elif key in stored:
+            stored[key][rows] = np.asarray(framed[key])
+    for s in (sim, root):
+        getattr(s, "_derived", {}).clear()
 
 
 class FilterBase(CalculatorBase):
@@ -332,7 +466,7 @@ class ParamView:
         return f"ParamView({self.__dict__!r})"
 
 
-class PropertyBase(CalculatorBase):
+class PropertyBase(_Arithmetic, CalculatorBase):
     """Calculator reading one value from the active snapshot
     (reference core/calculate/properties.py:125).
 
@@ -383,7 +517,7 @@ class PropertyBase(CalculatorBase):
         return None
 
     def _device_route(self, ctx: ExecutionContext, input: NodeInput, spec: dict):
-        if type(self).device_plan is PropertyBase.device_plan:
+        if type(self).device_plan is PropertyBase.device_plan or ctx.on_host:
             return NotImplemented
         # dynamic parameters are resolved on the snapshot the caller scoped:
         # one that depends on it keeps the two-step semantics behind a filter
@@ -410,38 +544,6 @@ class PropertyBase(CalculatorBase):
         if spec is None:
             return NotImplemented
         return self._device_route(ctx, input, spec)
-
-    # -- host-side arithmetic --------------------------------------------------
-    @classmethod
-    def as_property(cls, other) -> "PropertyBase":
-        return other if isinstance(other, PropertyBase) else ConstantProperty(other)
-
-    def __add__(self, other):
-        return OpProperty("add", self, self.as_property(other))
-
-    def __radd__(self, other):
-        return OpProperty("add", self.as_property(other), self)
-
-    def __sub__(self, other):
-        return OpProperty("sub", self, self.as_property(other))
-
-    def __rsub__(self, other):
-        return OpProperty("sub", self.as_property(other), self)
-
-    def __mul__(self, other):
-        return OpProperty("mul", self, self.as_property(other))
-
-    def __rmul__(self, other):
-        return OpProperty("mul", self.as_property(other), self)
-
-    def __truediv__(self, other):
-        return OpProperty("truediv", self, self.as_property(other))
-
-    def __rtruediv__(self, other):
-        return OpProperty("truediv", self.as_property(other), self)
-
-    def __neg__(self):
-        return OpProperty("neg", self)
 
     __hash__ = object.__hash__
 

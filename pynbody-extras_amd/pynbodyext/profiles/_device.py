@@ -50,6 +50,27 @@ class DeviceBins:
         self.has_selection = False
         self._csr = None
         self._kin = None  # registered (pos, vel) of the kinematic fields, kept alive
+        self._frame = None  # the frame set on the handle (None: none)
+
+    # -- frame ----------------------------------------------------------------
+    def set_frame(self, frame) -> None:
+        """The frame (pynbodyext.frame.Frame) the handle reads particles in:
+        honoured by the selections made after it and by the kinematic
+        fields; it stays across selections until ``set_frame(None)`` (or an
+        empty frame) clears it (pbx_profile_set_frame).  Only ``select``
+        takes a ``frame`` argument (and clears an earlier frame without one):
+        ``radial_equaln``, ``from_x`` / ``set_x`` and a handle reused through
+        ``into=`` keep whatever frame the handle holds.  The kinematic fields
+        read the frame held when they are evaluated: do not change it between
+        a selection and ``kinematic_field`` / ``kinematic_moments``."""
+        if frame is None or frame.empty:
+            if self._frame is not None:
+                nat.call("pbx_profile_set_frame", self._h, 0, None)
+            self._frame = None
+            return
+        packed = frame.packed()
+        nat.call("pbx_profile_set_frame", self._h, frame.flags, nat.dptr(packed))
+        self._frame = frame
 
     # -- construction -------------------------------------------------------
     @classmethod
@@ -70,7 +91,7 @@ class DeviceBins:
     @classmethod
     def select(cls, pos, mass=None, *, sphere=None, families=None, ndim: int = 3,
                on_device: bool = False, n: int | None = None,
-               into: "DeviceBins | None" = None) -> "DeviceBins":
+               into: "DeviceBins | None" = None, frame=None) -> "DeviceBins":
         """Fused mask + x + compaction.
 
         pos / mass: host (N,3) / (N,) float64 or float32 arrays (float32 is
@@ -78,9 +99,12 @@ class DeviceBins:
         snapshot), or float64 device pointers (``on_device=True``, then ``n``
         is required).  sphere: (cen, radius)
         or None.  families: list of (start, stop) index ranges or None.
-        ``into`` reuses an existing handle (and its HBM buffers).
+        ``into`` reuses an existing handle (and its HBM buffers).  frame: the
+        handle's frame from this selection on (None clears an earlier one;
+        float64 positions only).
         """
         d = into if into is not None else cls()
+        d.set_frame(frame)
         d.nbins, d._csr = None, None
         d._kin = None  # (a new selection clears the registration)
         # float32 snapshots stay float32 (no host up-cast; pbx_profile_select_typed)

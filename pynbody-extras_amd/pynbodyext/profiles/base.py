@@ -11,7 +11,11 @@ pynbodyext/filters), the mask, r (or rxy), the order-preserving
 compaction, the edges and the bin assignment all run in one GPU pipeline
 on the unfiltered snapshot's arrays; the masked sub-snapshot is then built
 from the kept indices.  Results are identical to filtering first (the
-device mask and r are bit-exact with numpy's).
+device mask and r are bit-exact with numpy's).  Inside a transform scope the
+snapshot is a FrameView: the handle then reads the base snapshot's arrays in
+the view's frame (pbx_profile_set_frame), and the profile's view is a view
+of the FrameView, so a host field such as ``prof["vx"]`` is the frame's,
+computed on demand; the device-covered fields never trigger that.
 """
 from __future__ import annotations
 
@@ -20,6 +24,7 @@ from typing import Any
 import numpy as np
 
 from ..calculate import CalculatorBase
+from ..frame import unframe
 from ..simcore import PendingField, SimSnap, SubSnap
 from ._device import KINEMATIC_FIELDS, DeviceBins
 from .bins import BinsSet
@@ -98,13 +103,17 @@ class RadialProfileBuilder(ProfileBuilderBase):
         if spec is None or "pos" not in getattr(source, "keys", lambda: [])():
             return NotImplemented
         params = self.resolve_dynamic_params(ctx, input)
+        # (a frame view: the base's own arrays go to the device with its frame)
+        raw, frame = unframe(source)
         with ctx.phase(self, "device select"):
             # float32 snapshots go to the device as float32 (no host copy):
             # r / rxy are then float32 values, exactly pynbody's derived array
-            pos = _native_float(source["pos"])
-            mass = _native_float(source["mass"]) if "mass" in source.keys() else None
+            pos = _native_float(raw["pos"])
+            mass = _native_float(raw["mass"]) if "mass" in raw.keys() else None
+            if frame is not None and pos.dtype != np.float64:
+                return NotImplemented  # (the device frame is float64 only)
             dev = DeviceBins.select(pos, mass, sphere=spec.get("sphere"),
-                                    families=spec.get("families"), ndim=self.ndim)
+                                    families=spec.get("families"), ndim=self.ndim, frame=frame)
             # the kept masses: read from the device (the same values: a copy,
             # through pinned chunks) instead of a host gather of the
             # sub-snapshot's column
@@ -131,7 +140,7 @@ class RadialProfileBuilder(ProfileBuilderBase):
             if root is not None:
                 def fetch_kin(name, dev=dev, root=root, idx=idx):
                     if name in root._arrays:  # (a user array stored since wins)
-                        return root._arrays[name][idx]
+                        return np.asarray(root._arrays[name])[idx]
                     register_kinematics(dev, root)
                     return dev.kinematic_field(name)
 

@@ -31,6 +31,7 @@ from typing import Union
 import numpy as np
 
 from .._pyn import IndexedSimArray, SimArray
+from ..frame import unframe
 from ..simcore import PendingField, SimSnap, SubSnap, is_pending
 from ._device import KINEMATIC_FIELDS, SRC_HOST, SRC_KIN, SRC_NONE, SRC_W, SRC_X
 
@@ -259,7 +260,8 @@ def kinematics_source(sim, dev):
             return None
     elif sim is not root or dev.n != len(root):
         return None
-    pos, vel = root._arrays.get("pos"), root._arrays.get("vel")
+    raw = unframe(root)[0]  # (a frame view: its base's arrays, read in the handle's frame)
+    pos, vel = raw._arrays.get("pos"), raw._arrays.get("vel")
     for a in (pos, vel):
         if a is None or a.dtype != np.float64 or a.shape != (len(root), 3):
             return None
@@ -276,9 +278,13 @@ def _stored(sim, name) -> bool:
 
 
 def register_kinematics(dev, root) -> None:
-    """Register the root's positions and velocities once per device handle."""
+    """Register the root's positions and velocities once per device handle
+    (a frame view: its base's, with the view's frame set on the handle)."""
     if not dev.has_kinematics:
-        dev.set_kinematics(root._arrays["pos"], root._arrays["vel"])
+        raw, frame = unframe(root)
+        if frame is not None:
+            dev.set_frame(frame)
+        dev.set_kinematics(raw._arrays["pos"], raw._arrays["vel"])
 
 
 def _kinematic_selector(profile, dev, name):

@@ -1,11 +1,12 @@
 """Device route of the property calculators (libpbx, csrc/property.hip).
 
-Thin ctypes wrappers of pbx_property_moments and pbx_property_shrink_center
-(include/pbx.h, "scalar properties"), and the conditions under which a
-property takes them: the source is a root ``SimSnap`` of the snapshot layer
-whose ``pos`` / ``vel`` / ``mass`` are float64 and C-contiguous and that
-stores no user array named ``vcxy`` or ``ke``.  Everything else runs the
-property's ``calculate`` on the host.
+Thin ctypes wrappers of pbx_property_moments(_frame) and
+pbx_property_shrink_center (include/pbx.h, "scalar properties"), and the
+conditions under which a property takes them: the source is a root
+``SimSnap`` of the snapshot layer — or a FrameView of one, whose frame then
+rides along in the pass — whose ``pos`` / ``vel`` / ``mass`` are float64 and
+C-contiguous and that stores no user array named ``vcxy`` or ``ke``.
+Everything else runs the property's ``calculate`` on the host.
 """
 from __future__ import annotations
 
@@ -15,6 +16,7 @@ from ctypes import byref, c_int64, c_void_p
 import numpy as np
 
 from .. import _native as nat
+from ..frame import FrameView, unframe
 from ..simcore import SimSnap, SubSnap
 
 # group bits and sum layout (pbx.h PBX_PROP_*)
@@ -71,19 +73,27 @@ def _scope_args(sphere, families):
 
 
 def moments(pos, vel, mass, *, groups: int, sphere=None, families=None, on_device: bool = False,
-            n: int | None = None) -> tuple[int, np.ndarray]:
+            n: int | None = None, frame=None) -> tuple[int, np.ndarray]:
     """(n_kept, sums[18]) of the kept particles in one device pass
     (pbx_property_moments): the count and the sums of the requested groups,
     the others 0.0.  pos / vel / mass: host arrays, or device pointers with
     ``on_device=True`` and ``n``; any of them may be None when no requested
-    group (and no sphere) reads it (mass None: unit masses)."""
+    group (and no sphere) reads it (mass None: unit masses).  frame (a
+    pynbodyext.frame.Frame): the pass reads the particles in it, the sphere's
+    centre is in its coordinates (pbx_property_moments_frame)."""
     ptrs, count, keep = _particle_args((pos, vel, mass), on_device, n)
     use_sphere, sph, fam, nfam = _scope_args(sphere, families)
     kept = c_int64(0)
     sums = np.zeros(NSUMS)
-    nat.call("pbx_property_moments", ptrs[0], ptrs[1], ptrs[2], count, int(on_device), use_sphere,
-             nat.dptr(sph), fam.ctypes.data_as(_i64p), nfam, int(groups), byref(kept),
-             nat.dptr(sums))
+    if frame is None or frame.empty:
+        nat.call("pbx_property_moments", ptrs[0], ptrs[1], ptrs[2], count, int(on_device),
+                 use_sphere, nat.dptr(sph), fam.ctypes.data_as(_i64p), nfam, int(groups),
+                 byref(kept), nat.dptr(sums))
+    else:
+        packed = frame.packed()
+        nat.call("pbx_property_moments_frame", ptrs[0], ptrs[1], ptrs[2], count, int(on_device),
+                 use_sphere, nat.dptr(sph), fam.ctypes.data_as(_i64p), nfam, int(groups),
+                 frame.flags, nat.dptr(packed), byref(kept), nat.dptr(sums))
     del keep
     return kept.value, sums
 
@@ -110,7 +120,7 @@ def shrink_center(pos, mass, *, r0: float, shrink_factor: float = 0.7, min_parti
 def snapshot_arrays(source, fields) -> dict | None:
     """The snapshot's arrays of ``fields`` when the device route may read
     them in place, else None (the property then runs on the host)."""
-    if not isinstance(source, SimSnap) or isinstance(source, SubSnap):
+    if not isinstance(source, SimSnap) or isinstance(source, (SubSnap, FrameView)):
         return None
     stored = source._arrays
     if "vcxy" in stored or "ke" in stored:  # a user's own column wins: host route
@@ -128,7 +138,9 @@ def snapshot_arrays(source, fields) -> dict | None:
 
 def moments_plan(prop, source, spec: dict):
     """Device plan of a property declaring ``device_groups`` and
-    ``finish(n_kept, sums, sim)``."""
+    ``finish(n_kept, sums, sim)``.  A FrameView source: its base's arrays
+    and its frame go to the pass; ``finish`` gets the view."""
+    base, frame = unframe(source)
     groups = prop.device_groups
     sphere, families = spec.get("sphere"), spec.get("families")
     fields = ["mass"] if groups != KAPPA_MEAN else []
@@ -136,13 +148,13 @@ def moments_plan(prop, source, spec: dict):
         fields.append("pos")
     if groups & VEL_GROUPS:
         fields.append("vel")
-    arrs = snapshot_arrays(source, fields)
+    arrs = snapshot_arrays(base, fields)
     if arrs is None:
         return None
 
     def run():
         n_kept, sums = moments(arrs.get("pos"), arrs.get("vel"), arrs.get("mass"), groups=groups,
-                               sphere=sphere, families=families, n=len(source))
+                               sphere=sphere, families=families, n=len(source), frame=frame)
         return prop.finish(n_kept, sums, source)
 
     return run

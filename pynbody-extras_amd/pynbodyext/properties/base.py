@@ -52,7 +52,7 @@ class ParamContain(PropertyBase):
     frac: cumulative fraction(s) in (0, 1), or a dynamic value; cal_key: the
     field to sort by; parameter: the weight field of the cumulative sum.
     The historical positional order ``ParamContain("r", 0.5)`` (field first)
-    is accepted as well.
+    is accepted as well, and so is the field alone, ``ParamContain("r")``.
     """
 
     frac: Param[float] = Param(default=0.5)
@@ -62,6 +62,8 @@ class ParamContain(PropertyBase):
     def __post_init__(self) -> None:
         if isinstance(self.frac, str) and not isinstance(self.cal_key, str):
             self.frac, self.cal_key = self.cal_key, self.frac
+        elif isinstance(self.frac, str):  # ParamContain("r"): the field alone, half of it
+            self.frac, self.cal_key = 0.5, self.frac
 
     def calculate(self, sim, params=None):
         frac = params.frac
@@ -83,7 +85,8 @@ class ParamContain(PropertyBase):
     def device_plan(self, source, spec, params):
         if params.cal_key not in ("r", "rxy") or params.parameter != "mass":
             return None
-        arrs = dev.snapshot_arrays(source, ("pos", "mass"))
+        base, frame = dev.unframe(source)  # (a FrameView: the handle reads its base in its frame)
+        arrs = dev.snapshot_arrays(base, ("pos", "mass"))
         if arrs is None:
             return None
         frac_array, frac_is_scalar = _normalize_frac(params.frac)
@@ -93,7 +96,7 @@ class ParamContain(PropertyBase):
 
             d = DeviceBins.select(arrs["pos"], arrs["mass"], sphere=spec.get("sphere"),
                                   families=spec.get("families"),
-                                  ndim=3 if params.cal_key == "r" else 2)
+                                  ndim=3 if params.cal_key == "r" else 2, frame=frame)
             try:
                 if d.n == 0:  # cumulative[-1] of the reference
                     raise IndexError("index -1 is out of bounds for axis 0 with size 0")
@@ -124,7 +127,7 @@ class ParamSum(PropertyBase):
         return sim[params.parameter].sum()
 
     def finish(self, n_kept, sums, sim):
-        return SimArray(sums[0], sim["mass"].units, sim=sim)
+        return SimArray(sums[0], sim._unit_of("mass"), sim=sim)
 
     def device_plan(self, source, spec, params):
         if params.parameter != "mass":

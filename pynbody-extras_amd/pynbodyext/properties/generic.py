@@ -72,13 +72,15 @@ class CenPos(_MomentProperty):
         return cen
 
     def finish(self, n_kept, sums, sim):
-        return SimArray(_ratio(sums[1:4], sums[0]), sim["pos"].units, sim=sim)
+        return SimArray(_ratio(sums[1:4], sums[0]), sim._unit_of("pos"), sim=sim)
 
     def device_plan(self, source, spec, params):
         if params.mode == "com":
             return dev.moments_plan(self, source, spec)
         if params.mode != "ssc" or spec.get("sphere") is not None:
             return None
+        # (inside a frame the shrinking sphere runs on the host: a FrameView
+        # is no root snapshot, pbx_property_shrink_center takes no frame)
         arrs = dev.snapshot_arrays(source, ("pos", "mass"))
         if arrs is None:
             return None
@@ -120,7 +122,7 @@ class CenVel(_MomentProperty):
         return cen
 
     def finish(self, n_kept, sums, sim):
-        return SimArray(_ratio(sums[4:7], sums[0]), sim["vel"].units, sim=sim)
+        return SimArray(_ratio(sums[4:7], sums[0]), sim._unit_of("vel"), sim=sim)
 
 
 @PropertyBase.dataclass
@@ -141,7 +143,7 @@ class AngMomVec(_MomentProperty):
         return angmom
 
     def finish(self, n_kept, sums, sim):
-        units = sim["mass"].units * sim["pos"].units * sim["vel"].units
+        units = sim._unit_of("mass") * sim._unit_of("pos") * sim._unit_of("vel")
         return SimArray(sums[7:10].copy(), units, sim=sim)
 
 
@@ -206,4 +208,4 @@ class PatternSpeed(_MomentProperty):
         with np.errstate(all="ignore"):
             I_minus = 1/2*(Ixx-Iyy)
             omega_Iz = 1/2*(I_minus*d_Ixy-d_I_minus*Ixy)/(I_minus*I_minus+Ixy*Ixy)
-        return SimArray(omega_Iz, sim["vel"].units / sim["pos"].units, sim=sim.ancestor)
+        return SimArray(omega_Iz, sim._unit_of("vel") / sim._unit_of("pos"), sim=sim.ancestor)

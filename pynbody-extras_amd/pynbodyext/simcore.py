@@ -17,7 +17,9 @@ path needs a stand-in for the few pieces of pynbody its callers touch:
 * what the property calculators read: the derived fields ``vcxy`` (the same
   expression and bits as ``vphi``) and ``ke = 0.5 * v2``,
   ``SimSnap.mean_by_mass`` and ``shrink_sphere_center`` (the stand-in for
-  pynbody.analysis.halo's, whose algorithm is restated there).
+  pynbody.analysis.halo's, whose algorithm is restated there);
+* ``calc_faceon_matrix`` (pynbody.analysis.angmom's construction, restated
+  there) for the transforms.
 
 When the real pynbody is importable, :mod:`pynbodyext._pyn` uses it instead.
 """
@@ -577,6 +579,20 @@ def shrink_sphere_r0(sim, r=None) -> float:
     if isinstance(r, (str, Unit)):
         return float(as_unit(r).ratio(sim["pos"].units))
     return float(r)
+
+
+def calc_faceon_matrix(angmom_vec, up=(0.0, 1.0, 0.0)) -> np.ndarray:
+    """The rotation that takes ``angmom_vec`` to +z (the stand-in for
+    pynbody.analysis.angmom.calc_faceon_matrix; this statement is its
+    contract): vec = angmom_vec / |vec|; p1 = cross(up, vec) / |..|;
+    p2 = cross(vec, p1); the rows are p1, p2, vec.  ``up`` must not be
+    parallel to the vector (transforms.AlignVec._safe_up sees to it)."""
+    vec = np.asarray(angmom_vec, dtype=np.float64).reshape(3)
+    vec = vec / np.sqrt((vec * vec).sum())
+    p1 = np.cross(np.asarray(up, dtype=np.float64).reshape(3), vec)
+    p1 = p1 / np.sqrt((p1 * p1).sum())
+    p2 = np.cross(vec, p1)
+    return np.stack((p1, p2, vec))
 
 
 # --------------------------------------------------------------------------
