@@ -439,6 +439,53 @@ int pbx_profile_kinematic_moments(void *handle, int n_fields, const int *codes, 
 #define PBX_FRAME_VEL 2
 #define PBX_FRAME_ROT 4
 int pbx_profile_set_frame(void *handle, int flags, const double *frame);
+/* The region a handle keeps particles in: a conjunction of nclauses <=
+ * PBX_REGION_MAX clauses, each one primitive (kinds[c]), negated when
+ * negate[c] != 0 (negate may be NULL: none), with its constants in
+ * params[c][0..5].  Per particle, in float64 without FMA contraction, in this
+ * order, on the coordinates the pass holds (after the frame when one is set;
+ * centres and corners are given in frame coordinates), every comparison
+ * strict, no periodic wrap:
+ *   kind                params                     kept when
+ *   PBX_REGION_SPHERE   cx, cy, cz, R^2            ((dx*dx + dy*dy) + dz*dz) < R^2
+ *   PBX_REGION_DISC     cx, cy, cz, R^2, h         (dx*dx + dy*dy) < R^2 && fabs(dz) < h
+ *   PBX_REGION_CUBOID   x1, y1, z1, x2, y2, z2     x > x1 && x < x2 && y > y1 && y < y2
+ *                                                  && z > z1 && z < z2
+ *   PBX_REGION_BAND     field, lo, hi, has_lo,     (!has_lo || f > lo) && (!has_hi || f < hi)
+ *                       has_hi
+ * with dx = x - cx (and so on), field one of PBX_BAND_X / _Y / _Z (the
+ * coordinate itself), PBX_BAND_R (f = sqrt((x*x + y*y) + z*z)) or
+ * PBX_BAND_RXY (f = sqrt(x*x + y*y)): a band compares the square root, not
+ * the square, as sim["r"] > lo does.  A negated clause is the logical NOT of
+ * its boolean, not the reversed comparison: a NaN coordinate fails a plain
+ * clause and passes a negated one (numpy's ~mask).  This restates
+ * pynbody.filt's Sphere, Disc, Cuboid, BandPass / HighPass / LowPass, and
+ * Annulus = Sphere(max) & ~Sphere(min), SolarNeighborhood = Disc(max, h) &
+ * ~Disc(min, h) as two clauses.
+ * Sticky: the region stays on the handle across selections until
+ * nclauses == 0 clears it.  Every later selection on the handle
+ * (pbx_profile_select, pbx_profile_select_typed, pbx_profile_radial_equaln on
+ * every path it takes) keeps a particle only when the region holds IN
+ * ADDITION TO its own use_sphere / fam arguments; the kinds, flags and
+ * constants are wave-uniform (the handle's device copy, read with scalar
+ * loads), and the kernels that evaluate them are instantiations of their
+ * own: without a region a selection runs the region-less code.  Set it before the selection it should
+ * apply to; an earlier selection is not recomputed.  With a region set,
+ * float32 positions in pbx_profile_select_typed and the distributed entry
+ * pbx_profile_radial_equaln_comm are a PBX_ERR_VALUE, and so are more than
+ * PBX_REGION_MAX clauses, an unknown kind and an unknown band field. */
+#define PBX_REGION_MAX 8
+#define PBX_REGION_SPHERE 1
+#define PBX_REGION_DISC 2
+#define PBX_REGION_CUBOID 3
+#define PBX_REGION_BAND 4
+#define PBX_BAND_X 0
+#define PBX_BAND_Y 1
+#define PBX_BAND_Z 2
+#define PBX_BAND_R 3
+#define PBX_BAND_RXY 4
+int pbx_profile_set_region(void *handle, int nclauses, const int *kinds, const int *negate,
+                           const double *params);
 /* One equaln radial-profile pass after pbx_profile_select with a single host
  * round trip (bins.py:720-746 edges, :346-395 assignment, the CSR when
  * build_csr, and per-bin sums of n_stats <= 16 requests (f_src / w_src in
@@ -632,6 +679,20 @@ int pbx_property_moments_frame(const double *pos, const double *vel, const doubl
                                int on_device, int use_sphere, const double *sphere,
                                const int64_t *fam, int nfam, uint32_t groups, int flags,
                                const double *frame, int64_t *n_kept, double *h_sums);
+/* The same pass in a frame and a region (nclauses / kinds / negate / params
+ * as in pbx_profile_set_region; nclauses == 0: exactly
+ * pbx_property_moments_frame).  A particle is kept when the families, the
+ * Sphere (if any) and every clause of the region hold, the clauses evaluated
+ * on the frame's coordinates.  pos is read whenever a region is present.  The
+ * region is a template parameter of the kernel beside the frame: the
+ * region-less instantiations are the ones the two entry points above launch.
+ * The summation order depends on the particle count alone. */
+int pbx_property_moments_region(const double *pos, const double *vel, const double *mass,
+                                int64_t n, int on_device, int use_sphere, const double *sphere,
+                                const int64_t *fam, int nfam, uint32_t groups, int flags,
+                                const double *frame, int nclauses, const int *kinds,
+                                const int *negate, const double *params, int64_t *n_kept,
+                                double *h_sums);
 /* Shrinking-sphere centre of the particles in the family ranges (all when
  * nfam = 0) — the centre CenPos("ssc") asks pynbody for
  * (properties/generic.py:54-55).  The particles are staged once (or

@@ -29,6 +29,7 @@
 
 #include "frame.h"
 #include "prims.h"
+#include "region.h"
 
 
 namespace pbx {
@@ -56,6 +57,11 @@ struct SelectParams {
   int64_t fam_lo[MAX_FAM];
   int64_t fam_hi[MAX_FAM];
   FrameHalf fr;  // the handle's frame for positions (pbx_profile_set_frame); float64 only
+  // the handle's region (pbx_profile_set_region), ANDed in by the kernels
+  // instantiated for one (null: none); float64 only.  A pointer to the
+  // handle's device copy, not the 400 bytes themselves: every kernel that
+  // takes a SelectParams would carry them in its arguments, region or not
+  const Region *rg;
 };
 
 // family membership of particle i (contiguous slices; no slices = all)
@@ -73,7 +79,11 @@ __device__ __forceinline__ bool in_family(int64_t i, const SelectParams &p) {
 // is evaluated in double on the exactly widened coordinates; r / rxy of the
 // float32 array stay float32 arithmetic (its float32 values are stored
 // widened, exactly).
-template <typename T>
+// RG: the kernel honours the handle's region (*p.rg, region.h; p.rg is then
+// not null).  The selection kernels are instantiated with and without it and
+// launched by whether a region is set, so that a region-less selection runs
+// the region-less code.
+template <typename T, bool RG>
 __device__ __forceinline__ bool select_xyz(T px, T py, T pz, const SelectParams &p, double &x) {
 #pragma clang fp contract(off)
   if constexpr (std::is_same<T, double>::value) {
@@ -86,7 +96,9 @@ __device__ __forceinline__ bool select_xyz(T px, T py, T pz, const SelectParams 
     if (p.sphere_origin) {
       const double r2 = (px * px + py * py) + pz * pz;
       x = __builtin_sqrt(r2);
-      return r2 < p.r2max;
+      bool keep = r2 < p.r2max;
+      if constexpr (RG) keep = keep & region_keep(*p.rg, px, py, pz);
+      return keep;
     }
   }
   bool keep = true;
@@ -94,6 +106,8 @@ __device__ __forceinline__ bool select_xyz(T px, T py, T pz, const SelectParams 
     double dx = (double)px - p.cx, dy = (double)py - p.cy, dz = (double)pz - p.cz;
     keep = ((dx * dx + dy * dy) + dz * dz) < p.r2max;
   }
+  // the handle's region on the same (frame) coordinates
+  if constexpr (RG && std::is_same<T, double>::value) keep = keep & region_keep(*p.rg, px, py, pz);
   const T r2 = (p.ndim == 2) ? (px * px + py * py) : ((px * px + py * py) + pz * pz);
   if constexpr (std::is_same<T, float>::value) x = (double)__builtin_sqrtf(r2);
   else x = __builtin_sqrt(r2);
@@ -127,7 +141,7 @@ constexpr uint64_t kStAgg = 1ull << 62, kStPre = 2ull << 62, kStVal = (1ull << 6
 // base + 64 * (64 t + j) ...) and the tile's output offset (toff[t]), from
 // which the weights and indices are materialised only when needed
 // (sel_materialize) and the assignment reads the masses directly.
-template <int BT, bool LAZY, typename T>
+template <int BT, bool LAZY, typename T, bool RG = false>
 __global__ void __launch_bounds__(BT)
     select_onepass(const T *__restrict__ pos, const void *__restrict__ mass, int64_t n,
                    SelectParams p, uint64_t *__restrict__ status, uint32_t *__restrict__ ctrl,
@@ -165,7 +179,7 @@ __global__ void __launch_bounds__(BT)
   }
 #pragma unroll
   for (int k = 0; k < SI; ++k) {
-    bool keep = ((inbits >> k) & 1u) && select_xyz(px[k], py[k], pz[k], p, xv[k]);
+    bool keep = ((inbits >> k) & 1u) && select_xyz<T, RG>(px[k], py[k], pz[k], p, xv[k]);
     keepbits |= (uint32_t)keep << k;
     c += (uint32_t)__popcll(__ballot(keep));
     if (keep) {
@@ -1121,7 +1135,7 @@ constexpr uint32_t SH_RSUB_MAX = 8;  // u16 count rows per block (flushed every 
 // whose geometry is the hint's, every kept key is also binned here: byte bin
 // by slot, per-bin sums in LDS (one slab row per block), the keys of
 // edge-holding digits into the block's deferred list.
-template <bool FAM, bool SPEC>
+template <bool FAM, bool SPEC, bool RG = false>
 __global__ void __launch_bounds__(SH_BT) __attribute__((amdgpu_waves_per_eu(4)))
     select_tiles(const double *__restrict__ pos, int64_t n, SelectParams p, uint32_t nt,
                  uint32_t G0, double *__restrict__ xo, uint64_t *__restrict__ kw,
@@ -1275,7 +1289,8 @@ __global__ void __launch_bounds__(SH_BT) __attribute__((amdgpu_waves_per_eu(4)))
 #pragma unroll
       for (int k = 0; k < SH_HALF; ++k) {
         double xv = 0.0;
-        const bool keep = ((H.in >> k) & 1u) && select_xyz(H.x[k], H.y[k], H.z[k], p, xv);
+        const bool keep =
+            ((H.in >> k) & 1u) && select_xyz<double, RG>(H.x[k], H.y[k], H.z[k], p, xv);
         const uint64_t bal = __ballot(keep);
         if (lane == 0) {
           kw[wj + k] = bal;
@@ -1407,7 +1422,8 @@ __global__ void __launch_bounds__(SH_BT) __attribute__((amdgpu_waves_per_eu(4)))
 #pragma unroll
     for (int k = 0; k < SH_HALF; ++k) {
       double xv = 0.0;
-      const bool keep = ((H.in >> k) & 1u) && select_xyz(H.x[k], H.y[k], H.z[k], p, xv);
+      const bool keep =
+          ((H.in >> k) & 1u) && select_xyz<double, RG>(H.x[k], H.y[k], H.z[k], p, xv);
       const uint64_t bal = __ballot(keep);
       // (the wave's 8 words stored from lanes 0..7 once per tile instead:
       // 265 vs 268 us at 64M, no gain, round 6 — and one store per half
@@ -1576,7 +1592,7 @@ __global__ void __launch_bounds__(SH_BT) __attribute__((amdgpu_waves_per_eu(4)))
 // hflag): the call re-reads x, the results are the same.  The last block
 // writes the hint and re-arms the scratch (mm2 = [~min, max], done).
 constexpr int SMP_BT = 256, SMP_PER = 4;  // samples per thread, their loads in flight together
-template <bool FAM>
+template <bool FAM, bool RG = false>
 __global__ void __launch_bounds__(SMP_BT)
     sample_hint(const double *__restrict__ pos, int64_t n, SelectParams p, int64_t span,
                 uint32_t S, uint64_t ka, uint64_t kb, uint64_t kub,
@@ -1600,7 +1616,7 @@ __global__ void __launch_bounds__(SMP_BT)
 #pragma unroll
   for (int u = 0; u < SMP_PER; ++u) {
     double xv = 0.0;
-    if (in[u] && select_xyz(px[u], py[u], pz[u], p, xv)) {
+    if (in[u] && select_xyz<double, RG>(px[u], py[u], pz[u], p, xv)) {
       const uint64_t k = dkey(xv);
       if (k >= ka && k <= kb) {
         kmin = k < kmin ? k : kmin;
@@ -1686,7 +1702,9 @@ __device__ void xsrc_tiles(const XSrc &xs, uint32_t ta, uint32_t tb) {
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       double xv = 0.0;
-      if (kp[u] && select_xyz(px[u], py[u], pz[u], xs.sp, xv)) xs.x[a + (int64_t)u * bt] = xv;
+      // (a kept slot passed the region when its keep bit was set: not evaluated again)
+      if (kp[u] && select_xyz<double, false>(px[u], py[u], pz[u], xs.sp, xv))
+        xs.x[a + (int64_t)u * bt] = xv;
     }
   }
 }
@@ -3671,6 +3689,7 @@ __device__ void mono_done(const MonoArgs &a, int tagpos) {
   do {                                                                      \
     if (a.trace && threadIdx.x == 0) a.trace[blockIdx.x * 8 + (k)] = wall_clock64(); \
   } while (0)
+template <bool RG = false>  // RG: evaluates the handle's region (select_xyz)
 __global__ void __launch_bounds__(MONO_BT) radial_mono(MonoArgs a) {
   static_assert(MONO_SI == 4 && MONO_NW == 16, "4 particles per lane, 16 waves");
   MONO_STAMP(0);
@@ -3749,7 +3768,8 @@ __global__ void __launch_bounds__(MONO_BT) radial_mono(MonoArgs a) {
     bool esc = false;
 #pragma unroll
     for (int k = 0; k < MONO_SI; ++k) {
-      const bool keep = ((inbits >> k) & 1u) && select_xyz(px[k], py[k], pz[k], a.sp, xv[k]);
+      const bool keep =
+          ((inbits >> k) & 1u) && select_xyz<double, RG>(px[k], py[k], pz[k], a.sp, xv[k]);
       keepbits |= (uint32_t)keep << k;
       bal[k] = __ballot(keep);
       if (keep) {
@@ -4907,6 +4927,9 @@ struct Profile {
   // pbx_profile_set_frame: how the handle reads particles (sticky across
   // selections; every flag off = no frame)
   Frame frame{};
+  // pbx_profile_set_region: the region every selection ANDs in (sticky; n == 0 = none)
+  Region region{};
+  Buf rgdev;  // its device copy (what SelectParams points to)
   bool posst_sel = false;  // posst holds this selection's positions (a lazy selection of host arrays)
 };
 
@@ -5265,6 +5288,9 @@ static SelPrep select_prep(Profile &P, hipStream_t st, const SelectReq &q, bool 
   if (pos_f32 && P.frame.any())
     fail(PBX_ERR_VALUE, "a frame is set on this handle: float32 positions are not supported");
   sp.fr = P.frame.pos;
+  if (pos_f32 && P.region.any())
+    fail(PBX_ERR_VALUE, "a region is set on this handle: float32 positions are not supported");
+  sp.rg = P.region.any() ? (const Region *)P.rgdev.p : nullptr;
   sp.mass_f32 = mass_f32;
   const size_t ps = pos_f32 ? sizeof(float) : sizeof(double);
   const size_t ms = mass_f32 ? sizeof(float) : sizeof(double);
@@ -5366,6 +5392,7 @@ static uint32_t select_launch(Profile &P, hipStream_t st, const SelectReq &q, bo
   if (!persist) PBX_HIP(hipMemsetAsync(stat, 0, sizeof(uint64_t) * nst, st));
   else if (!tail_zero) PBX_HIP(hipMemsetAsync(stat + nt, 0, sizeof(uint64_t) * (nst - nt), st));
   if (span) {
+    const bool rgn = sp.rg != nullptr;
     auto go = [&](auto kern, int bt, auto tp) {
       using T = decltype(tp);
       hipLaunchKernelGGL(kern, dim3(nt), dim3(bt), 0, st, (const T *)d_pos, d_mass, hi, sp, stat,
@@ -5375,7 +5402,10 @@ static uint32_t select_launch(Profile &P, hipStream_t st, const SelectReq &q, bo
       if (nt < 1024) go(select_onepass<1024, false, float>, 1024, 0.0f);
       else go(select_onepass<TPB, false, float>, TPB, 0.0f);
     } else if (nt < 1024) {
-      if (lazy) go(select_onepass<1024, true, double>, 1024, 0.0);
+      if (rgn) {  // (the instantiations that evaluate the region, select_xyz)
+        if (lazy) go(select_onepass<1024, true, double, true>, 1024, 0.0);
+        else go(select_onepass<1024, false, double, true>, 1024, 0.0);
+      } else if (lazy) go(select_onepass<1024, true, double>, 1024, 0.0);
       else go(select_onepass<1024, false, double>, 1024, 0.0);
     } else {
       // 512-thread tiles (8 particles per lane, 64 VGPRs: 8 waves per SIMD):
@@ -5434,18 +5464,26 @@ static uint32_t select_launch(Profile &P, hipStream_t st, const SelectReq &q, bo
             if (std::isfinite(ub)) kub = dkey(ub);
           }
           unsigned long long *smm = (unsigned long long *)P.shs.p;
-          auto sk = sp.nfam > 1 ? sample_hint<true> : sample_hint<false>;
+          auto sk = rgn ? (sp.nfam > 1 ? sample_hint<true, true> : sample_hint<false, true>)
+                        : (sp.nfam > 1 ? sample_hint<true> : sample_hint<false>);
           hipLaunchKernelGGL(sk, dim3(ceil_div(S, SMP_BT * SMP_PER)), dim3(SMP_BT), 0, st, (const double *)d_pos,
                              hi, sp, span, S, th->ka, th->kb, kub, smm, (unsigned *)(smm + 2),
                              (SelHint *)th->hint);
         }
         auto kern = spec ? (sp.nfam > 1 ? select_tiles<true, true> : select_tiles<false, true>)
                          : (sp.nfam > 1 ? select_tiles<true, false> : select_tiles<false, false>);
+        if (rgn)
+          kern = spec ? (sp.nfam > 1 ? select_tiles<true, true, true> : select_tiles<false, true, true>)
+                      : (sp.nfam > 1 ? select_tiles<true, false, true>
+                                     : select_tiles<false, false, true>);
         hipLaunchKernelGGL(kern, dim3(G1),
                            dim3(SH_BT), 0, st, (const double *)d_pos, hi,
                            sp, nt, (uint32_t)G0, xo, kw, r.kpre, wc, toff, bt, mm,
                            th ? th->hint : nullptr, th ? th->ka : 0ull, th ? th->kb : ~0ull, rows16, rsub,
                            (uint32_t *)(mm + 2 * MM_SLOTS), sa);
+      } else if (rgn) {
+        if (lazy) go(select_onepass<512, true, double, true>, 512, 0.0);
+        else go(select_onepass<512, false, double, true>, 512, 0.0);
       } else if (lazy) go(select_onepass<512, true, double>, 512, 0.0);
       else go(select_onepass<512, false, double>, 512, 0.0);
     }
@@ -5713,11 +5751,13 @@ static uint32_t mono_max_tiles(int dev) {
   std::lock_guard<std::mutex> lk(mu);
   if ((int)cache.size() <= dev) cache.resize((size_t)dev + 1, -1);
   if (cache[(size_t)dev] < 0) {
-    int cus = 0, per = 0;
+    int cus = 0, per = 0, per_rg = 0;  // (both instantiations must fit)
     PBX_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
     PBX_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(
-        &per, reinterpret_cast<const void *>(&radial_mono), MONO_BT, 0));
-    cache[(size_t)dev] = per >= 1 ? std::min<int>(cus, (int)MONO_MAXT) : 0;
+        &per, reinterpret_cast<const void *>(&radial_mono<false>), MONO_BT, 0));
+    PBX_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(
+        &per_rg, reinterpret_cast<const void *>(&radial_mono<true>), MONO_BT, 0));
+    cache[(size_t)dev] = std::min(per, per_rg) >= 1 ? std::min<int>(cus, (int)MONO_MAXT) : 0;
   }
   return (uint32_t)cache[(size_t)dev];
 }
@@ -5826,7 +5866,8 @@ static double *radial_mono_run(Profile &P, hipStream_t st, const SelectReq &q, i
   a.eU = (uint32_t *)P.meue.p;
   a.eE = a.eU + RADIX + 1;
   a.eg = (P.medge_next && nq == P.medge_nq) ? 1 : 0;
-  hipLaunchKernelGGL(radial_mono, dim3(nt), dim3(MONO_BT), 0, st, a);
+  if (a.sp.rg) hipLaunchKernelGGL(radial_mono<true>, dim3(nt), dim3(MONO_BT), 0, st, a);
+  else hipLaunchKernelGGL(radial_mono<false>, dim3(nt), dim3(MONO_BT), 0, st, a);
   PBX_HIP(hipGetLastError());
   P.bar_done += nt;
   ++P.n_mono;
@@ -6585,7 +6626,7 @@ int pbx_profile_destroy(void *handle) {
                   &p->swc, &p->sbt, &p->mono, &p->bar,
                   &p->mono_trace, &p->dscal, &p->dlc, &p->pdone, &p->pstage, &p->mH,
                   &p->mhint, &p->stab, &p->srec, &p->sspec, &p->sslab, &p->sflag, &p->posst,
-                  &p->slteq, &p->mpedges, &p->meue, &p->kpos, &p->kvel};
+                  &p->slteq, &p->mpedges, &p->meue, &p->kpos, &p->kvel, &p->rgdev};
     for (Buf *b : all) b->release();
     p->pin.release();
     p->mpin.release();
@@ -6974,6 +7015,22 @@ int pbx_profile_set_frame(void *handle, int flags, const double *frame) {
   });
 }
 
+// The region every later selection on the handle ANDs into its predicate
+// (region.h; select_prep -> select_xyz).  Sticky; nclauses == 0 clears it.
+int pbx_profile_set_region(void *handle, int nclauses, const int *kinds, const int *negate,
+                           const double *params) {
+  return with_profile(handle, [&](Profile &P, Device &d, hipStream_t st) {
+    P.region = region_of(nclauses, kinds, negate, params);
+    // (stream-ordered after the kernels of earlier selections that read the
+    // old one; waited for, since the source is the handle's own member)
+    if (P.region.any()) {
+      PBX_HIP(hipMemcpyAsync(P.rgdev.get(sizeof(Region)), &P.region, sizeof(Region),
+                             hipMemcpyHostToDevice, st));
+      PBX_HIP(hipStreamSynchronize(st));
+    }
+  });
+}
+
 // Field `code` of the kept particles, in selection order, to the host
 // (P.n doubles): the per-particle read behind sub["vr"].
 int pbx_profile_kinematic_field(void *handle, int code, double *h_out) {
@@ -7171,6 +7228,8 @@ static int radial_equaln_entry(void *comm, void *handle, const SelectReq &q, int
     const CommRanks cr = comm ? comm_ranks(comm) : CommRanks{1, 0};
     if (comm && P.frame.any())
       fail(PBX_ERR_VALUE, "a frame is set on this handle: the distributed profile takes none");
+    if (comm && P.region.any())
+      fail(PBX_ERR_VALUE, "a region is set on this handle: the distributed profile takes none");
     check_stat_args(nbins, stats);
     Device &d = current_device();
     std::unique_lock<std::mutex> lk(d.mu);  // (released inside comm_allreduce's host wait)

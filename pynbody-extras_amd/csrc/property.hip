@@ -22,6 +22,7 @@
 
 #include "frame.h"
 #include "pbx_common.h"
+#include "region.h"
 
 namespace pbx {
 namespace prop {
@@ -78,13 +79,15 @@ __device__ __forceinline__ bool prop_in_sphere(double x, double y, double z, con
 // reads positions / velocities at all (a sphere or a position group; a
 // velocity group).  FRAME: what was read is taken to the frame `fr` before
 // the sphere test and the terms (frame.h); without it fr is not looked at and
-// the pass is the frame-less one.  part: one row of NS sums per block; cnt:
-// its count.
-template <bool POS, bool VEL, bool FRAME>
+// the pass is the frame-less one.  REGION (POS only): the clauses of rg are
+// ANDed into the predicate on the same coordinates (region.h); without it rg
+// is not looked at and the pass is the region-less one.  part: one row of NS
+// sums per block; cnt: its count.
+template <bool POS, bool VEL, bool FRAME, bool REGION = false>
 __global__ void __launch_bounds__(PROP_TPB)
     property_moments(const double *__restrict__ pos, const double *__restrict__ vel,
-                     const double *__restrict__ mass, PropParams p, Frame fr, uint32_t groups,
-                     double *__restrict__ part, long long *__restrict__ cnt) {
+                     const double *__restrict__ mass, PropParams p, Frame fr, Region rg,
+                     uint32_t groups, double *__restrict__ part, long long *__restrict__ cnt) {
 #pragma clang fp contract(off)
   __shared__ double ws[PROP_NW][NS];
   __shared__ long long wc[PROP_NW];
@@ -128,6 +131,10 @@ __global__ void __launch_bounds__(PROP_TPB)
     if (p.use_sphere) {
 #pragma unroll
       for (int k = 0; k < PROP_ITEMS; ++k) keep[k] = keep[k] && prop_in_sphere(x[k], y[k], z[k], p);
+    }
+    if constexpr (REGION && POS) {
+#pragma unroll
+      for (int k = 0; k < PROP_ITEMS; ++k) keep[k] = keep[k] & region_keep(rg, x[k], y[k], z[k]);
     }
     // the masses of the kept particles only
 #pragma unroll
@@ -277,6 +284,7 @@ struct Staged {
   PropParams p{};
   const double *pos = nullptr, *vel = nullptr, *mass = nullptr;
   Frame fr{};  // (all flags off: the frame-less kernels)
+  Region rg{};  // (no clauses: the region-less kernels)
 };
 
 static const double *stage(Device &d, hipStream_t st, const double *a, int width, int64_t lo,
@@ -320,16 +328,22 @@ static void run_pass(Device &d, hipStream_t st, const Staged &s, uint32_t groups
                      .ensure(sizeof(double) * ((size_t)PROP_MAX_BLOCKS * (NS + 1) + PROP_NOUT));
   long long *cnt = (long long *)(part + (size_t)PROP_MAX_BLOCKS * NS);
   double *out = part + (size_t)PROP_MAX_BLOCKS * (NS + 1);
-  const bool use_pos = s.p.use_sphere || (groups & POS_GROUPS);
+  const bool use_pos = s.p.use_sphere || s.rg.any() || (groups & POS_GROUPS);
   const bool use_vel = (groups & VEL_GROUPS) != 0;
   auto launch = [&](auto kern) {
     hipLaunchKernelGGL(kern, dim3(grid), dim3(PROP_TPB), 0, st, s.pos, s.vel, s.mass, s.p, s.fr,
-                       groups, part, cnt);
+                       s.rg, groups, part, cnt);
   };
   // (a frame half whose array the pass does not read changes nothing)
   const bool framed = (use_pos && (s.fr.pos.shift || s.fr.pos.rot)) ||
                       (use_vel && (s.fr.vel.shift || s.fr.vel.rot));
-  if (framed) {
+  if (s.rg.any()) {  // (a region reads positions)
+    if (framed) {
+      if (use_vel) launch(property_moments<true, true, true, true>);
+      else launch(property_moments<true, false, true, true>);
+    } else if (use_vel) launch(property_moments<true, true, false, true>);
+    else launch(property_moments<true, false, false, true>);
+  } else if (framed) {
     if (use_pos && use_vel) launch(property_moments<true, true, true>);
     else if (use_pos) launch(property_moments<true, false, true>);
     else launch(property_moments<false, true, true>);
@@ -356,11 +370,14 @@ using namespace pbx::prop;
 
 extern "C" {
 
-int pbx_property_moments_frame(const double *pos, const double *vel, const double *mass, int64_t n,
-                               int on_device, int use_sphere, const double *sphere,
-                               const int64_t *fam, int nfam, uint32_t groups, int flags,
-                               const double *frame, int64_t *n_kept, double *h_sums) {
+int pbx_property_moments_region(const double *pos, const double *vel, const double *mass,
+                                int64_t n, int on_device, int use_sphere, const double *sphere,
+                                const int64_t *fam, int nfam, uint32_t groups, int flags,
+                                const double *frame, int nclauses, const int *kinds,
+                                const int *negate, const double *params, int64_t *n_kept,
+                                double *h_sums) {
   return guard([&] {
+    const Region rg = region_of(nclauses, kinds, negate, params);
     if (flags & ~(PBX_FRAME_POS | PBX_FRAME_VEL | PBX_FRAME_ROT))
       fail(PBX_ERR_VALUE, "flags must be a mask of PBX_FRAME_* bits (got 0x%x)", flags);
     if (!n_kept || !h_sums) fail(PBX_ERR_VALUE, "null output");
@@ -370,13 +387,13 @@ int pbx_property_moments_frame(const double *pos, const double *vel, const doubl
     if ((groups & VEL_GROUPS) && !vel)
       fail(PBX_ERR_VALUE, "the requested groups read velocities: vel is NULL");
     if (use_sphere && !sphere) fail(PBX_ERR_VALUE, "use_sphere without a sphere");
-    if ((use_sphere || (groups & POS_GROUPS)) && !pos)
-      fail(PBX_ERR_VALUE, "a sphere or the requested groups read positions: pos is NULL");
+    if ((use_sphere || rg.any() || (groups & POS_GROUPS)) && !pos)
+      fail(PBX_ERR_VALUE, "a sphere, a region or the requested groups read positions: pos is NULL");
     Device &d = current_device();
     std::lock_guard<std::mutex> lk(d.mu);
     hipStream_t st = d.stream;
     ScopedTimer tm("pbx.property.moments");
-    const bool use_pos = use_sphere || (groups & POS_GROUPS);
+    const bool use_pos = use_sphere || rg.any() || (groups & POS_GROUPS);
     const bool use_vel = (groups & VEL_GROUPS) != 0;
     Staged s = stage_particles(d, st, use_pos ? pos : nullptr, use_vel ? vel : nullptr, mass, n,
                                on_device, fam, nfam);
@@ -388,8 +405,18 @@ int pbx_property_moments_frame(const double *pos, const double *vel, const doubl
       s.p.r2max = sphere[3];
     }
     s.fr = frame_of(flags, frame);
+    s.rg = rg;
     run_pass(d, st, s, groups, n_kept, h_sums);
   });
+}
+
+int pbx_property_moments_frame(const double *pos, const double *vel, const double *mass, int64_t n,
+                               int on_device, int use_sphere, const double *sphere,
+                               const int64_t *fam, int nfam, uint32_t groups, int flags,
+                               const double *frame, int64_t *n_kept, double *h_sums) {
+  return pbx_property_moments_region(pos, vel, mass, n, on_device, use_sphere, sphere, fam, nfam,
+                                     groups, flags, frame, 0, nullptr, nullptr, nullptr, n_kept,
+                                     h_sums);
 }
 
 int pbx_property_moments(const double *pos, const double *vel, const double *mass, int64_t n,

@@ -172,6 +172,10 @@ _SIGNATURES: dict[str, tuple] = {
     "pbx_profile_set_frame": (c_int, [c_void_p, c_int, _dp]),
     "pbx_property_moments_frame": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int,
                                            _dp, _i64p, c_int, c_uint32, c_int, _dp, _i64p, _dp]),
+    "pbx_profile_set_region": (c_int, [c_void_p, c_int, POINTER(c_int), POINTER(c_int), _dp]),
+    "pbx_property_moments_region": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int,
+                                            _dp, _i64p, c_int, c_uint32, c_int, _dp, c_int,
+                                            POINTER(c_int), POINTER(c_int), _dp, _i64p, _dp]),
     "pbx_property_shrink_center": (c_int, [c_void_p, c_void_p, c_int64, c_int, _i64p, c_int,
                                            c_double, c_double, c_int64, _dp, _i64p, _i64p]),
     "pbx_comm_unique_id_size": (c_int, []),

@@ -360,8 +360,9 @@ class FilterBase(CalculatorBase):
         return self.value(sim)
 
     def device_spec(self, sim):
-        """Device-fusable description ({"sphere": (cen, r), "families": [...]})
-        or None when this filter cannot be fused."""
+        """Device-fusable description ({"sphere": (cen, r), "families": [...],
+        "region": [clauses of pynbodyext.region]}) or None when this filter
+        cannot be fused."""
         return None
 
     def __and__(self, other: "FilterBase") -> "AndFilter":
@@ -382,21 +383,34 @@ class AndFilter(FilterBase):
         return ctx.raw_value(self.f1, input) & ctx.raw_value(self.f2, input)
 
     def device_spec(self, sim):
-        s1, s2 = self.f1.device_spec(sim), self.f2.device_spec(sim)
-        if s1 is None or s2 is None:
-            return None
-        if "sphere" in s1 and "sphere" in s2:
-            return None
-        out = {}
-        sph = s1.get("sphere") or s2.get("sphere")
-        if sph is not None:
-            out["sphere"] = sph
-        f1, f2 = s1.get("families"), s2.get("families")
-        if f1 is not None and f2 is not None:
-            out["families"] = _intersect_ranges(f1, f2)
-        elif f1 is not None or f2 is not None:
-            out["families"] = f1 if f1 is not None else f2
-        return out
+        return and_specs(self.f1.device_spec(sim), self.f2.device_spec(sim))
+
+
+def and_specs(s1, s2):
+    """The device_spec of the conjunction of two (None when either is, or
+    when the region would exceed the library's clause limit).  The first
+    Sphere keeps the sphere slot; a second one becomes a region clause."""
+    from . import region as rg
+
+    if s1 is None or s2 is None:
+        return None
+    out = {}
+    clauses = list(s1.get("region") or ()) + list(s2.get("region") or ())
+    sph = s1.get("sphere") or s2.get("sphere")
+    if sph is not None:
+        out["sphere"] = sph
+    if "sphere" in s1 and "sphere" in s2:
+        clauses.append(rg.sphere_clause(*s2["sphere"]))
+    if len(clauses) > rg.REGION_MAX:
+        return None
+    if clauses:
+        out["region"] = clauses
+    f1, f2 = s1.get("families"), s2.get("families")
+    if f1 is not None and f2 is not None:
+        out["families"] = _intersect_ranges(f1, f2)
+    elif f1 is not None or f2 is not None:
+        out["families"] = f1 if f1 is not None else f2
+    return out
 
 
 class OrFilter(FilterBase):
@@ -420,6 +434,20 @@ class NotFilter(FilterBase):
 
     def execute(self, ctx, input):
         return ~ctx.raw_value(self.f, input)
+
+    def device_spec(self, sim):
+        """The negated clause of a spec that is exactly one clause (a lone
+        sphere or a one-clause region); anything else is not fusable."""
+        from . import region as rg
+
+        s = self.f.device_spec(sim)
+        if s is None or len(s) != 1:
+            return None
+        if "sphere" in s:
+            return {"region": [rg.sphere_clause(*s["sphere"], negate=True)]}
+        if len(s.get("region") or ()) == 1:
+            return {"region": [rg.negated(s["region"][0])]}
+        return None
 
 
 def _intersect_ranges(a, b):

@@ -13,6 +13,7 @@ from ctypes import byref, c_double, c_int, c_int64, c_uint32, c_uint64, c_void_p
 import numpy as np
 
 from .. import _native as nat
+from .. import region as rg
 
 NMOM = 7  # Σw, Σf·w, Σf²·w, Σf, Σf², Σ|f|·w, Σ|f|
 ALL_COLS = (1 << NMOM) - 1
@@ -51,6 +52,7 @@ class DeviceBins:
         self._csr = None
         self._kin = None  # registered (pos, vel) of the kinematic fields, kept alive
         self._frame = None  # the frame set on the handle (None: none)
+        self._region = None  # the region clauses set on the handle (None: none)
 
     # -- frame ----------------------------------------------------------------
     def set_frame(self, frame) -> None:
@@ -72,6 +74,25 @@ class DeviceBins:
         nat.call("pbx_profile_set_frame", self._h, frame.flags, nat.dptr(packed))
         self._frame = frame
 
+    # -- region ---------------------------------------------------------------
+    def set_region(self, region) -> None:
+        """The region (a list of pynbodyext.region clauses, at most 8) every
+        later selection on the handle keeps particles in, in addition to its
+        sphere and families; None or an empty list clears it
+        (pbx_profile_set_region).  ``select`` and ``radial_equaln`` always set
+        or clear it from their ``region`` argument."""
+        if not region:
+            if self._region is not None:
+                nat.call("pbx_profile_set_region", self._h, 0, None, None, None)
+            self._region = None
+            return
+        region = list(region)
+        if region == self._region:
+            return
+        n, kinds, neg, params = rg.packed(region)
+        nat.call("pbx_profile_set_region", self._h, n, kinds, neg, nat.dptr(params))
+        self._region = region
+
     # -- construction -------------------------------------------------------
     @classmethod
     def from_x(cls, x) -> "DeviceBins":
@@ -91,7 +112,7 @@ class DeviceBins:
     @classmethod
     def select(cls, pos, mass=None, *, sphere=None, families=None, ndim: int = 3,
                on_device: bool = False, n: int | None = None,
-               into: "DeviceBins | None" = None, frame=None) -> "DeviceBins":
+               into: "DeviceBins | None" = None, frame=None, region=None) -> "DeviceBins":
         """Fused mask + x + compaction.
 
         pos / mass: host (N,3) / (N,) float64 or float32 arrays (float32 is
@@ -101,10 +122,14 @@ class DeviceBins:
         or None.  families: list of (start, stop) index ranges or None.
         ``into`` reuses an existing handle (and its HBM buffers).  frame: the
         handle's frame from this selection on (None clears an earlier one;
-        float64 positions only).
+        float64 positions only).  region: the handle's region from this
+        selection on (a list of pynbodyext.region clauses ANDed with the
+        sphere and the families; None clears an earlier one; float64
+        positions only).
         """
         d = into if into is not None else cls()
         d.set_frame(frame)
+        d.set_region(region)
         d.nbins, d._csr = None, None
         d._kin = None  # (a new selection clears the registration)
         # float32 snapshots stay float32 (no host up-cast; pbx_profile_select_typed)
@@ -166,7 +191,7 @@ class DeviceBins:
     def radial_equaln(cls, pos, mass=None, *, nbins: int, sphere=None, families=None,
                       ndim: int = 3, bin_min=None, bin_max=None, stats=(), csr=True,
                       on_device: bool = False, n: int | None = None,
-                      into: "DeviceBins | None" = None, comm=None):
+                      into: "DeviceBins | None" = None, comm=None, region=None):
         """select() followed by binned_equaln() with ONE host round trip
         (pbx_profile_radial_equaln).  Returns (handle, edges, counts, moments)
         with the same values and errors as the two calls.
@@ -186,17 +211,22 @@ class DeviceBins:
         may then bin with the stored table and keep no copy of x, the first
         later reader of x (selection(x=True), statistics of x, percentiles)
         recomputing it from ``pos``.  Host arrays are staged into the handle
-        and carry no such contract."""
+        and carry no such contract.
+
+        ``region``: as in ``select`` (set or cleared on the handle by every
+        call; not with ``comm`` or float32 arrays)."""
         if comm is None and not on_device and (
                 np.asarray(pos).dtype == np.float32 or
                 (mass is not None and np.asarray(mass).dtype == np.float32)):
             # float32 snapshots: r in float32 arithmetic exactly as select()
             # computes it (the one-sync kernels read float64 only), then the
             # same binning pass — identical to select() + binned_equaln()
-            d = cls.select(pos, mass, sphere=sphere, families=families, ndim=ndim, into=into)
+            d = cls.select(pos, mass, sphere=sphere, families=families, ndim=ndim, into=into,
+                           region=region)
             edges, counts, mom = d.binned_equaln(nbins, bin_min, bin_max, stats, csr)
             return d, edges, counts, [m.copy() for m in mom]
         d = into if into is not None else cls()
+        d.set_region(region)
         d.nbins, d._csr = None, None
         d._kin = None  # (a new selection clears the registration)
         nq = int(nbins) + 1

@@ -110,10 +110,11 @@ class RadialProfileBuilder(ProfileBuilderBase):
             # r / rxy are then float32 values, exactly pynbody's derived array
             pos = _native_float(raw["pos"])
             mass = _native_float(raw["mass"]) if "mass" in raw.keys() else None
-            if frame is not None and pos.dtype != np.float64:
-                return NotImplemented  # (the device frame is float64 only)
+            if (frame is not None or spec.get("region")) and pos.dtype != np.float64:
+                return NotImplemented  # (the device frame and region are float64 only)
             dev = DeviceBins.select(pos, mass, sphere=spec.get("sphere"),
-                                    families=spec.get("families"), ndim=self.ndim, frame=frame)
+                                    families=spec.get("families"), ndim=self.ndim, frame=frame,
+                                    region=spec.get("region"))
             # the kept masses: read from the device (the same values: a copy,
             # through pinned chunks) instead of a host gather of the
             # sub-snapshot's column

@@ -1,6 +1,13 @@
 """Property calculators (reference pynbodyext/properties)."""
 
-from .base import ParamContain, ParameterContain, ParamSum, PropertyBase
+from .base import (
+    ParamContain,
+    ParameterContain,
+    ParamSum,
+    PropertyBase,
+    SurfaceDensity,
+    VolumeDensity,
+)
 from .generic import AngMomVec, CenPos, CenVel, KappaRot, KappaRotMean, PatternSpeed
 
 __all__ = [
@@ -8,6 +15,8 @@ __all__ = [
     "ParamSum",
     "ParamContain",
     "ParameterContain",
+    "VolumeDensity",
+    "SurfaceDensity",
     "KappaRot",
     "KappaRotMean",
     "CenPos",

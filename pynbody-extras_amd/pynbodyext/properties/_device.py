@@ -1,6 +1,6 @@
 """Device route of the property calculators (libpbx, csrc/property.hip).
 
-Thin ctypes wrappers of pbx_property_moments(_frame) and
+Thin ctypes wrappers of pbx_property_moments(_frame, _region) and
 pbx_property_shrink_center (include/pbx.h, "scalar properties"), and the
 conditions under which a property takes them: the source is a root
 ``SimSnap`` of the snapshot layer — or a FrameView of one, whose frame then
@@ -16,6 +16,7 @@ from ctypes import byref, c_int64, c_void_p
 import numpy as np
 
 from .. import _native as nat
+from .. import region as rg
 from ..frame import FrameView, unframe
 from ..simcore import SimSnap, SubSnap
 
@@ -73,19 +74,30 @@ def _scope_args(sphere, families):
 
 
 def moments(pos, vel, mass, *, groups: int, sphere=None, families=None, on_device: bool = False,
-            n: int | None = None, frame=None) -> tuple[int, np.ndarray]:
+            n: int | None = None, frame=None, region=None) -> tuple[int, np.ndarray]:
     """(n_kept, sums[18]) of the kept particles in one device pass
     (pbx_property_moments): the count and the sums of the requested groups,
     the others 0.0.  pos / vel / mass: host arrays, or device pointers with
     ``on_device=True`` and ``n``; any of them may be None when no requested
     group (and no sphere) reads it (mass None: unit masses).  frame (a
     pynbodyext.frame.Frame): the pass reads the particles in it, the sphere's
-    centre is in its coordinates (pbx_property_moments_frame)."""
+    centre is in its coordinates (pbx_property_moments_frame).  region (a
+    list of pynbodyext.region clauses): ANDed with the sphere and the
+    families, on the frame's coordinates (pbx_property_moments_region; pos is
+    then required)."""
     ptrs, count, keep = _particle_args((pos, vel, mass), on_device, n)
     use_sphere, sph, fam, nfam = _scope_args(sphere, families)
     kept = c_int64(0)
     sums = np.zeros(NSUMS)
-    if frame is None or frame.empty:
+    if region:
+        framed = frame is not None and not frame.empty
+        packed = frame.packed() if framed else None
+        nc, kinds, neg, params = rg.packed(region)
+        nat.call("pbx_property_moments_region", ptrs[0], ptrs[1], ptrs[2], count, int(on_device),
+                 use_sphere, nat.dptr(sph), fam.ctypes.data_as(_i64p), nfam, int(groups),
+                 frame.flags if framed else 0, nat.dptr(packed), nc, kinds, neg,
+                 nat.dptr(params), byref(kept), nat.dptr(sums))
+    elif frame is None or frame.empty:
         nat.call("pbx_property_moments", ptrs[0], ptrs[1], ptrs[2], count, int(on_device),
                  use_sphere, nat.dptr(sph), fam.ctypes.data_as(_i64p), nfam, int(groups),
                  byref(kept), nat.dptr(sums))
@@ -142,9 +154,9 @@ def moments_plan(prop, source, spec: dict):
     and its frame go to the pass; ``finish`` gets the view."""
     base, frame = unframe(source)
     groups = prop.device_groups
-    sphere, families = spec.get("sphere"), spec.get("families")
+    sphere, families, region = spec.get("sphere"), spec.get("families"), spec.get("region")
     fields = ["mass"] if groups != KAPPA_MEAN else []
-    if sphere is not None or groups & POS_GROUPS:
+    if sphere is not None or region or groups & POS_GROUPS:
         fields.append("pos")
     if groups & VEL_GROUPS:
         fields.append("vel")
@@ -154,7 +166,8 @@ def moments_plan(prop, source, spec: dict):
 
     def run():
         n_kept, sums = moments(arrs.get("pos"), arrs.get("vel"), arrs.get("mass"), groups=groups,
-                               sphere=sphere, families=families, n=len(source), frame=frame)
+                               sphere=sphere, families=families, n=len(source), frame=frame,
+                               region=region)
         return prop.finish(n_kept, sums, source)
 
     return run

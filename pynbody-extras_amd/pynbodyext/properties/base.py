@@ -1,13 +1,15 @@
 """Base property calculators — reference pynbodyext/properties/base.py.
 
-``ParamSum(parameter)`` and ``ParamContain(frac, cal_key, parameter)`` (alias
-``ParameterContain``) with the reference's ``calculate`` on the host.  The
-density-style properties of the reference module (VolumeDensity,
-SurfaceDensity, RadiusAtSurfaceDensity) need Annulus / BandPass filters and
-are not provided.
+``ParamSum(parameter)``, ``ParamContain(frac, cal_key, parameter)`` (alias
+``ParameterContain``), ``VolumeDensity(rmax, parameter, rmin)`` and
+``SurfaceDensity(rmax, rmin, parameter)`` with the reference's ``calculate``
+on the host.  RadiusAtSurfaceDensity (a bisection over a sorted cumulative
+sum) is not provided.
 
 Device route (MI355X): ``ParamSum("mass")`` is the mass group of the
-property pass (csrc/property.hip); ``ParamContain`` by ``"r"`` / ``"rxy"``
+property pass (csrc/property.hip); the two densities of ``"mass"`` are the
+same pass with the scope's predicate ANDed with an Annulus / an rxy band
+(two region clauses / one, csrc/region.h); ``ParamContain`` by ``"r"`` / ``"rxy"``
 with mass weights is the fused selection followed by the containment of its
 whole x (csrc/profile.hip, pbx_profile_contain): the stable sort by radius,
 the sequential cumulative mass, np.interp — the reference's values bit for
@@ -20,10 +22,12 @@ from typing import Any
 import numpy as np
 
 from .._pyn import SimArray
-from ..calculate import Param, PropertyBase
+from ..calculate import Param, PropertyBase, and_specs
+from ..filters import Annulus, BandPass
 from . import _device as dev
 
-__all__ = ["PropertyBase", "ParamSum", "ParamContain", "ParameterContain"]
+__all__ = ["PropertyBase", "ParamSum", "ParamContain", "ParameterContain", "VolumeDensity",
+           "SurfaceDensity"]
 
 
 def _normalize_frac(frac: Any) -> tuple[np.ndarray, bool]:
@@ -96,7 +100,8 @@ class ParamContain(PropertyBase):
 
             d = DeviceBins.select(arrs["pos"], arrs["mass"], sphere=spec.get("sphere"),
                                   families=spec.get("families"),
-                                  ndim=3 if params.cal_key == "r" else 2, frame=frame)
+                                  ndim=3 if params.cal_key == "r" else 2, frame=frame,
+                                  region=spec.get("region"))
             try:
                 if d.n == 0:  # cumulative[-1] of the reference
                     raise IndexError("index -1 is out of bounds for axis 0 with size 0")
@@ -133,3 +138,73 @@ class ParamSum(PropertyBase):
         if params.parameter != "mass":
             return None
         return dev.moments_plan(self, source, spec)
+
+
+class _DensityPass:
+    """The mass group of one property pass divided by a volume or an area."""
+
+    device_groups = dev.MASS
+
+    def __init__(self, extent: float, dim: int):
+        self.extent, self.dim = extent, dim
+
+    def finish(self, n_kept, sums, sim):
+        return _density(sums[0], self.extent, "mass", self.dim, sim)
+
+
+def _density(total, extent, parameter, dim, sim) -> SimArray:
+    with np.errstate(all="ignore"):  # (an empty shell: x/0 as numpy gives)
+        value = np.float64(total) / np.float64(extent)
+    return SimArray(value, sim._unit_of(parameter) / sim._unit_of("pos") ** dim, sim=sim.ancestor)
+
+
+@PropertyBase.dataclass
+class VolumeDensity(PropertyBase):
+    """Mean volume density of the shell rmin <= r < rmax
+    (reference properties/base.py:121-142): the sum of ``parameter`` over
+    ``Annulus(rmin, rmax)`` divided by the Annulus volume."""
+
+    rmax: Param[float] = Param(field_name="pos")
+    parameter: str = "mass"
+    rmin: Param[float] = Param(default=0.0, field_name="pos")
+
+    def calculate(self, sim, params=None):
+        selector = Annulus(params.rmin, params.rmax)
+        param_sum = np.asarray(sim[selector][params.parameter]).sum()
+        return _density(param_sum, selector.volume(sim), params.parameter, 3, sim)
+
+    def device_plan(self, source, spec, params):
+        if params.parameter != "mass":
+            return None
+        selector = Annulus(params.rmin, params.rmax)
+        scoped = and_specs(spec, selector.device_spec(source))
+        if scoped is None:
+            return None
+        return dev.moments_plan(_DensityPass(selector.volume(source), 3), source, scoped)
+
+
+@PropertyBase.dataclass
+class SurfaceDensity(PropertyBase):
+    """Mean surface density of the ring rmin < rxy < rmax (reference
+    properties/base.py:144-169): the sum of ``parameter`` over
+    ``BandPass("rxy", rmin, rmax)`` divided by pi (rmax^2 - rmin^2)."""
+
+    rmax: Param[float] = Param(field_name="pos")
+    rmin: Param[float] = Param(default=0.0, field_name="pos")
+    parameter: str = "mass"
+
+    def calculate(self, sim, params=None):
+        selector = BandPass("rxy", params.rmin, params.rmax)
+        param_sum = np.asarray(sim[selector][params.parameter]).sum()
+        area = np.pi * (params.rmax ** 2 - params.rmin ** 2)
+        return _density(param_sum, area, params.parameter, 2, sim)
+
+    def device_plan(self, source, spec, params):
+        if params.parameter != "mass":
+            return None
+        selector = BandPass("rxy", params.rmin, params.rmax)
+        scoped = and_specs(spec, selector.device_spec(source))
+        if scoped is None:
+            return None
+        area = np.pi * (params.rmax ** 2 - params.rmin ** 2)
+        return dev.moments_plan(_DensityPass(area, 2), source, scoped)

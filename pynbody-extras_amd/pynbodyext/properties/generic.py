@@ -10,7 +10,7 @@ final arithmetic to the count and the 18 sums in ``finish``; the sums come
 from one pass over the root snapshot's pos / vel / mass with the Sphere /
 family predicate applied in the same pass (csrc/property.hip).
 CenPos("ssc") runs the shrinking-sphere loop over data that stays on the
-device when the scope has no Sphere of its own.  The value's ``.sim`` is the
+device when the scope has no Sphere or region of its own.  The value's ``.sim`` is the
 root snapshot there (the masked sub-snapshot is never built).
 """
 from __future__ import annotations
@@ -77,7 +77,7 @@ class CenPos(_MomentProperty):
     def device_plan(self, source, spec, params):
         if params.mode == "com":
             return dev.moments_plan(self, source, spec)
-        if params.mode != "ssc" or spec.get("sphere") is not None:
+        if params.mode != "ssc" or spec.get("sphere") is not None or spec.get("region"):
             return None
         # (inside a frame the shrinking sphere runs on the host: a FrameView
         # is no root snapshot, pbx_property_shrink_center takes no frame)

@@ -13,7 +13,8 @@ path needs a stand-in for the few pieces of pynbody its callers touch:
   (pynbody/derived.py evaluates ``(pos**2).sum(axis=1) ** 0.5``, which
   numpy computes as exactly this expression followed by a correctly rounded
   sqrt);
-* ``filt`` — Sphere / FamilyFilter / And / Or / Not masks;
+* ``filt`` — Sphere / FamilyFilter / Cuboid / Disc / Annulus / SolarNeighborhood /
+  BandPass / HighPass / LowPass / And / Or / Not masks;
 * what the property calculators read: the derived fields ``vcxy`` (the same
   expression and bits as ``vphi``) and ``ke = 0.5 * v2``,
   ``SimSnap.mean_by_mass`` and ``shrink_sphere_center`` (the stand-in for
@@ -29,6 +30,8 @@ import re
 from fractions import Fraction
 
 import numpy as np
+
+from . import region as _region
 
 # --------------------------------------------------------------------------
 # units
@@ -651,6 +654,78 @@ class Sphere(Filter):
         return ((dx * dx + dy * dy) + dz * dz) < self.radius * self.radius
 
 
+class _Region(Filter):
+    """A conjunction of region clauses of the positions (pynbodyext/region.py:
+    the arithmetic of the device passes, restated in numpy)."""
+
+    def __init__(self, clauses):
+        self.clauses = list(clauses)
+
+    def __call__(self, sim):
+        return _region.region_mask(np.asarray(sim["pos"]), self.clauses)
+
+
+class Cuboid(_Region):
+    """x1 < x < x2, y1 < y < y2, z1 < z < z2; Cuboid(x1) is the cube (x1, -x1)^3."""
+
+    def __init__(self, x1, y1=None, z1=None, x2=None, y2=None, z2=None):
+        y1 = x1 if y1 is None else y1
+        z1 = x1 if z1 is None else z1
+        x2 = -x1 if x2 is None else x2
+        y2 = -y1 if y2 is None else y2
+        z2 = -z1 if z2 is None else z2
+        super().__init__([_region.cuboid_clause(x1, y1, z1, x2, y2, z2)])
+
+
+class Disc(_Region):
+    """(dx*dx + dy*dy) < radius^2 and |dz| < height."""
+
+    def __init__(self, radius, height, cen=(0, 0, 0)):
+        super().__init__([_region.disc_clause(cen, radius, height)])
+
+
+class Annulus(_Region):
+    """Sphere(r2, cen) & ~Sphere(r1, cen)."""
+
+    def __init__(self, r1, r2, cen=(0, 0, 0)):
+        super().__init__([_region.sphere_clause(cen, r2),
+                          _region.sphere_clause(cen, r1, negate=True)])
+
+
+class SolarNeighborhood(_Region):
+    """Disc(r2, height, cen) & ~Disc(r1, height, cen)."""
+
+    def __init__(self, r1, r2, height, cen=(0, 0, 0)):
+        super().__init__([_region.disc_clause(cen, r2, height),
+                          _region.disc_clause(cen, r1, height, negate=True)])
+
+
+class BandPass(Filter):
+    """min < sim[prop] < max."""
+
+    def __init__(self, prop, min, max):
+        self.prop, self.min, self.max = prop, min, max
+
+    def __call__(self, sim):
+        f = np.asarray(sim[self.prop])
+        m = np.ones(len(f), dtype=bool)
+        if self.min is not None:
+            m &= f > self.min
+        if self.max is not None:
+            m &= f < self.max
+        return m
+
+
+class HighPass(BandPass):
+    def __init__(self, prop, min):
+        super().__init__(prop, min, None)
+
+
+class LowPass(BandPass):
+    def __init__(self, prop, max):
+        super().__init__(prop, None, max)
+
+
 class FamilyFilter(Filter):
     def __init__(self, family):
         self.family = get_family(family)
@@ -668,3 +743,10 @@ class filt:  # namespace mirroring pynbody.filt
     Not = Not
     Sphere = Sphere
     FamilyFilter = FamilyFilter
+    Cuboid = Cuboid
+    Disc = Disc
+    Annulus = Annulus
+    SolarNeighborhood = SolarNeighborhood
+    BandPass = BandPass
+    HighPass = HighPass
+    LowPass = LowPass
