@@ -90,8 +90,11 @@ __device__ __forceinline__ void pair(double dx, double dy, double dz, double m, 
   if (KERN == 1) {
     // spline (kernel.rs:47-54,71-80): inside the support replace the
     // Newtonian values, expressed in the same scaled units
+    // (a NaN softening — f64::max of two NaNs, direct.rs:395,472 — is neither
+    // <= 0 nor reached by r: it takes the spline branch and the result is
+    // NaN, as in kernel.rs where w2(NaN) falls through to -1/u)
     double r = s2 * (0.5 * w);
-    if (h > 0.0 && r < h) {
+    if (!(h <= 0.0) && !(r >= h)) {
       double hinv = 1.0 / h;
       double u = r * hinv;
       mw = -2.0 * m * (w2_inner(u) * hinv);
@@ -125,15 +128,17 @@ __device__ __forceinline__ void sweep(const double4 *__restrict__ src,
       double dy = s.y - yi[k];
       double dz = s.z - zi[k];
       double m = s.w;
+      double h = 0.0;
+      if (KERN >= 0) h = __builtin_fmax(hi[k], hj);
       if (CHECK) {
         // the self pair contributes nothing: zero mass and a unit distance
-        // keep 0 * inf out of the force
+        // keep 0 * inf out of the force, no softening keeps a particle's own
+        // NaN softening (fmax(NaN, NaN)) out of 0 * NaN
         bool self = (j == me[k]);
         m = self ? 0.0 : m;
         dx = self ? 1.0 : dx;
+        if (KERN >= 0) h = self ? 0.0 : h;
       }
-      double h = 0.0;
-      if (KERN >= 0) h = __builtin_fmax(hi[k], hj);
       pair<KERN, WANT>(dx, dy, dz, m, h, ph[k], ax[k], ay[k], az[k]);
     }
   }
