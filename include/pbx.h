@@ -614,8 +614,9 @@ int pbx_profile_percentiles(void *handle, int f_src, const double *h_f, int w_sr
  * (the reference's default np.argsort leaves their order open).  The
  * cumulative sum runs sequentially on one lane on purpose: that reproduces
  * np.cumsum's rounding bit for bit.  Its cost grows linearly with the
- * selection and is unmeasured; a parallel scan would trade the bit parity
- * away and is left for later. */
+ * selection (about 20 ns per element on an MI355X,
+ * profiles/radius_at_density/README.md); a parallel scan would trade the bit
+ * parity away and is left for later. */
 int pbx_profile_contain(void *handle, int w_src, const double *h_w, int nq, const double *q,
                         double *h_out, double *denom);
 
@@ -764,6 +765,62 @@ int pbx_comm_max_f64(void *comm, double value, double *out);
 typedef int (*pbx_host_collective_fn)(void *ctx, int kind, void *h_buf, int64_t count, int dtype,
                                       int op, const int64_t *counts, const int64_t *displs);
 int pbx_comm_init_host(void **comm, int nranks, int rank, pbx_host_collective_fn fn, void *ctx);
+
+/* ------------------------------------------------------------------ */
+/* cumulative table of a profile handle: RadiusAtSurfaceDensity        */
+/* ------------------------------------------------------------------ */
+/* Replaces RadiusAtSurfaceDensity.calculate (properties/base.py:172-284):
+ * the radii sorted, the cumulative mass in that order, the surface density
+ * read off the two (_sigma_at_radius), a scan of 256 radii for the first
+ * sign change of sigma - target and 80 bisection steps.
+ *
+ * pbx_profile_cum_build runs after a selection or after pbx_profile_set_x:
+ * the stable value sort of the handle's whole x (the one
+ * pbx_profile_contain launches; ties keep index order), then one block
+ * writes two arrays of n doubles kept on the handle,
+ *     xs[k] = x[e[k]],  cum[k] = np.cumsum(w[e])[k]
+ * with e the sorted element ids and the sum running sequentially on one
+ * lane (np.cumsum's rounding, bit for bit; linear in n, see
+ * pbx_profile_contain), from one element on.  w_src = 1 (the selection
+ * weights) or 2 (the host array h_w, n doubles in selection order).
+ * *r_min = xs[0], *r_max = xs[n-1], *total = cum[n-1].  n == 0 is a
+ * PBX_ERR_VALUE.  Whatever replaces the handle's x drops the table: a new
+ * selection (pbx_profile_select*, pbx_profile_radial_equaln*),
+ * pbx_profile_set_x, pbx_profile_set_frame, pbx_profile_set_region.
+ *
+ * pbx_profile_cum_get reads the table back (n doubles each).
+ *
+ * pbx_profile_cum_sigma: h_sigma[k] = _sigma_at_radius of h_r[k], 1 <= nr
+ * <= 4096, one thread per radius; mode 1 = "total" (M(<=r) / (pi r^2)),
+ * mode 0 = the shell [max(r - eps/2, 0), r + eps/2].  Every statement of
+ * the reference in its order, without FMA contraction: the r <= 0, hi <= 0,
+ * hi <= lo and area <= 0 guards, searchsorted right for the outer radius
+ * and left for the inner one, cum[hi-1] - (lo > 0 ? cum[lo-1] : 0.0),
+ * pi * (rout^2 - rin^2) with both squares rounded first.  A square is the
+ * rounded product r*r (the reference's r**2 on scalars is libm pow, which
+ * differs from the product by one ulp for about 0.085 % of doubles).
+ *
+ * pbx_profile_cum_solve: ONE launch of one 256-thread block and ONE
+ * read-back.  The threads evaluate sigma on the uploaded grid (2 <= ngrid <=
+ * 4096 radii) into LDS; the block finds the first k with
+ * signbit(sigma[k] - target) != signbit(sigma[k+1] - target); one lane then
+ * runs the reference's loop from left = grid[k], right = grid[k+1]: up to 80
+ * times mid = 0.5*(left + right), stop with left = right = mid when
+ * |sigma(mid) - target| < 1e-10, else right = mid when
+ * (sigma(left) - target) * (sigma(mid) - target) <= 0 and left = mid
+ * otherwise.  *radius = 0.5*(left + right).  info[4] = {status (0 solved, 1
+ * no sign change: *radius is NaN), k, iterations run (the one that stopped
+ * early included), 1 if it stopped early}.
+ *
+ * PBX_ERR_VALUE: a NULL argument, nr / ngrid out of range, a mode other
+ * than 0 or 1, and cum_get / cum_sigma / cum_solve without a valid table. */
+int pbx_profile_cum_build(void *handle, int w_src, const double *h_w, double *r_min,
+                          double *r_max, double *total);
+int pbx_profile_cum_get(void *handle, double *h_xs, double *h_cum);
+int pbx_profile_cum_sigma(void *handle, int mode, double eps, int nr, const double *h_r,
+                          double *h_sigma);
+int pbx_profile_cum_solve(void *handle, int mode, double eps, double target, int ngrid,
+                          const double *h_grid, double *radius, int64_t *info);
 
 #ifdef __cplusplus
 }

@@ -4753,6 +4753,35 @@ __device__ double np_interp1(double x, const XP &xp, const FP &fp, int64_t len) 
 
 constexpr int PCT_CH = 2048;  // weights per LDS chunk of the sequential cumsum
 
+// One chunk of np.cumsum on the calling lane: cs[i] = the running sum after
+// ws[i], i < len, carried in from c and returned (first: the sum starts at
+// ws[0] itself, like np.cumsum, not at 0.0 + ws[0]).  ws / cs are LDS.
+__device__ __forceinline__ double cumsum_chunk(double c, bool first, int len, const double *ws,
+                                               double *cs) {
+#pragma clang fp contract(off)
+  int i = 0;
+  if (first) {
+    c = ws[0];
+    cs[0] = c;
+    i = 1;
+  }
+  for (; i + 8 <= len; i += 8) {
+    double v[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] = ws[i + j];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      c = c + v[j];
+      cs[i + j] = c;
+    }
+  }
+  for (; i < len; ++i) {
+    c = c + ws[i];
+    cs[i] = c;
+  }
+  return c;
+}
+
 // One block per bin.  e: element ids sorted by (bin, value); off: bin
 // offsets into e; q: the nq fractions p/100.  Weighted: the cumulative sum
 // runs on ONE lane in the reference's order (np.cumsum is sequential, so
@@ -4778,28 +4807,7 @@ pct_bins(const int32_t *__restrict__ e, const int64_t *__restrict__ off,
       const int len = (int)std::min<int64_t>(PCT_CH, m - base);
       for (int i = tid; i < len; i += TPB) ws[i] = w[e[o + base + i]];
       __syncthreads();
-      if (tid == 0) {
-        int i = 0;
-        if (base == 0) {
-          c = ws[0];
-          cs[0] = c;
-          i = 1;
-        }
-        for (; i + 8 <= len; i += 8) {
-          double v[8];
-#pragma unroll
-          for (int j = 0; j < 8; ++j) v[j] = ws[i + j];
-#pragma unroll
-          for (int j = 0; j < 8; ++j) {
-            c = c + v[j];
-            cs[i + j] = c;
-          }
-        }
-        for (; i < len; ++i) {
-          c = c + ws[i];
-          cs[i] = c;
-        }
-      }
+      if (tid == 0) c = cumsum_chunk(c, base == 0, len, ws, cs);
       __syncthreads();
       for (int i = tid; i < len; i += TPB) cdf[o + base + i] = cs[i];
       __syncthreads();
@@ -4829,6 +4837,150 @@ pct_bins(const int32_t *__restrict__ e, const int64_t *__restrict__ off,
   }
 }
 
+// ------------------------------------------- cumulative table and its solver
+// RadiusAtSurfaceDensity (properties/base.py:172-284): the selection's radii
+// in stable value order with the cumulative sum of the weights in that order,
+// the surface density read off that table, and the reference's bracketing
+// scan and bisection over it.
+
+// One block.  e: element ids in stable value order of x; xs[k] = x[e[k]],
+// cum[k] = np.cumsum(w[e])[k] (one lane, in index order, from one element on).
+__global__ void __launch_bounds__(TPB)
+cum_table(const int32_t *__restrict__ e, const double *__restrict__ x,
+          const double *__restrict__ w, int64_t n, double *__restrict__ xs,
+          double *__restrict__ cum) {
+#pragma clang fp contract(off)
+  __shared__ double ws[PCT_CH];
+  __shared__ double cs[PCT_CH];
+  const int tid = threadIdx.x;
+  double c = 0.0;
+  for (int64_t base = 0; base < n; base += PCT_CH) {
+    const int len = (int)std::min<int64_t>(PCT_CH, n - base);
+    for (int i = tid; i < len; i += TPB) {
+      const int32_t j = e[base + i];
+      ws[i] = w[j];
+      xs[base + i] = x[j];
+    }
+    __syncthreads();
+    if (tid == 0) c = cumsum_chunk(c, base == 0, len, ws, cs);
+    __syncthreads();
+    for (int i = tid; i < len; i += TPB) cum[base + i] = cs[i];
+    __syncthreads();
+  }
+}
+
+// np.searchsorted(xs, v, side): numpy's order, NaN behind every number
+__device__ __forceinline__ bool np_less(double a, double b) {
+  return a < b || (b != b && a == a);
+}
+
+template <bool RIGHT>
+__device__ int64_t np_searchsorted(const double *__restrict__ xs, int64_t n, double v) {
+  int64_t lo = 0, hi = n;
+  while (lo < hi) {
+    const int64_t mid = lo + ((hi - lo) >> 1);
+    const double m = xs[mid];
+    const bool below = RIGHT ? !np_less(v, m) : np_less(m, v);
+    if (below) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo;
+}
+
+// _sigma_at_radius (properties/base.py:196-228), statement by statement;
+// mode 1 = "total", 0 = the shell [r - eps/2, r + eps/2].  The squares are
+// the rounded products r*r.
+__device__ double cum_sigma_at(double r, const double *__restrict__ xs,
+                               const double *__restrict__ cum, int64_t n, double eps, int mode) {
+#pragma clang fp contract(off)
+  constexpr double PI = 3.141592653589793;
+  if (r <= 0) return 0.0;
+  if (mode == 1) {
+    const int64_t hi = np_searchsorted<true>(xs, n, r);
+    if (hi <= 0) return 0.0;
+    const double m_inside = cum[hi - 1];
+    const double area = PI * (r * r);
+    return area <= 0 ? 0.0 : m_inside / area;
+  }
+  const double rlow = r - 0.5 * eps;
+  const double rin = (0.0 > rlow) ? 0.0 : rlow;  // max(rlow, 0.0) of Python
+  const double rout = r + 0.5 * eps;
+  if (rout <= 0) return 0.0;
+  const int64_t lo = np_searchsorted<false>(xs, n, rin);
+  const int64_t hi = np_searchsorted<true>(xs, n, rout);
+  if (hi <= 0 || hi <= lo) return 0.0;
+  const double m_shell = cum[hi - 1] - (lo > 0 ? cum[lo - 1] : 0.0);
+  const double a_out = rout * rout, a_in = rin * rin;
+  const double area = PI * (a_out - a_in);
+  return area <= 0 ? 0.0 : m_shell / area;
+}
+
+__global__ void __launch_bounds__(TPB)
+cum_sigma_kernel(const double *__restrict__ xs, const double *__restrict__ cum, int64_t n,
+                 double eps, int mode, const double *__restrict__ r, int nr,
+                 double *__restrict__ out) {
+  const int t = blockIdx.x * TPB + threadIdx.x;
+  if (t < nr) out[t] = cum_sigma_at(r[t], xs, cum, n, eps, mode);
+}
+
+constexpr int CUM_MAXGRID = 4096;  // radii per cum_sigma / cum_solve call
+constexpr int CUM_ITERS = 80;      // bisection steps of the reference
+
+// One block.  sigma on the grid into LDS, the first sign change of sigma -
+// target along it, then the reference's bisection on one lane
+// (properties/base.py:261-281).  out: [radius][status, bracket index,
+// iterations run, broke early] (the last four int64).
+__global__ void __launch_bounds__(TPB)
+cum_solve_kernel(const double *__restrict__ xs, const double *__restrict__ cum, int64_t n,
+                 double eps, int mode, double target, const double *__restrict__ grid, int ngrid,
+                 double *__restrict__ out) {
+#pragma clang fp contract(off)
+  __shared__ double sig[CUM_MAXGRID];
+  __shared__ int first;
+  const int tid = threadIdx.x;
+  if (tid == 0) first = ngrid;
+  for (int k = tid; k < ngrid; k += TPB) sig[k] = cum_sigma_at(grid[k], xs, cum, n, eps, mode);
+  __syncthreads();
+  for (int k = tid; k + 1 < ngrid; k += TPB) {
+    if (__builtin_signbit(sig[k] - target) != __builtin_signbit(sig[k + 1] - target)) {
+      atomicMin(&first, k);
+      break;  // (this lane's later k are larger)
+    }
+  }
+  __syncthreads();
+  if (tid != 0) return;
+  int64_t *info = (int64_t *)(out + 1);
+  const int k0 = first;
+  if (k0 >= ngrid) {
+    out[0] = __builtin_nan("");
+    info[0] = 1;
+    info[1] = -1;
+    info[2] = 0;
+    info[3] = 0;
+    return;
+  }
+  double left = grid[k0], right = grid[k0 + 1];
+  int it = 0, broke = 0;
+  while (it < CUM_ITERS) {
+    ++it;
+    const double mid = 0.5 * (left + right);
+    const double s_mid = cum_sigma_at(mid, xs, cum, n, eps, mode);
+    if (__builtin_fabs(s_mid - target) < 1e-10) {
+      left = right = mid;
+      broke = 1;
+      break;
+    }
+    const double s_left = cum_sigma_at(left, xs, cum, n, eps, mode);
+    if ((s_left - target) * (s_mid - target) <= 0) right = mid;
+    else left = mid;
+  }
+  out[0] = 0.5 * (left + right);
+  info[0] = 0;
+  info[1] = k0;
+  info[2] = it;
+  info[3] = broke;
+}
+
 // ----------------------------------------------------------------- handle
 struct MselState {  // radix select in progress (equaln)
   bool active = false;
@@ -4855,6 +5007,12 @@ struct Profile {
   Buf x, w, idx, bins, perm, keys0, keys1, vtmp, hist, tsum, edges, counts, minmax, slab, acc,
       field, weight, ranks, bounds;
   Buf pk0, pk1, pv0, pv1, pbk, pcdf, poff, pq, pout;  // order statistics
+  // pbx_profile_cum_build: x in stable value order and the cumulative weights
+  // (cum_n doubles each), the radii of a cum_sigma / cum_solve call, their
+  // results; whatever replaces x clears cum_valid
+  Buf cxs, ccum, cgrid, cres;
+  bool cum_valid = false;
+  int64_t cum_n = 0;
   Buf fctl, fseg, fgrp, fslab, fpack, frec, fblk, bins8;  // one-sync equaln path
   bool bins_in8 = false;  // the last assignment's bins are bytes in bins8 (ensure_bins32)
   // lazy selection (select_launch): keep words, tile offsets, staged masses
@@ -5360,6 +5518,7 @@ struct TileHist {  // select_tiles' hinted level-0 histogram (null hint: none)
 
 static uint32_t select_launch(Profile &P, hipStream_t st, const SelectReq &q, bool lazy = false,
                               bool tiled = false, TileHist *th = nullptr) {
+  P.cum_valid = false;  // (x is rewritten from here on)
   const SelPrep r = select_prep(P, st, q, lazy, tiled);
   const int pos_f32 = q.pos_f32;
   const SelectParams &sp = r.sp;
@@ -5540,6 +5699,7 @@ static void ensure_x(Profile &P, hipStream_t st) {
 
 // the handle's state after a selection of `kept` particles (key range in P.mm)
 static void select_commit(Profile &P, int64_t kept) {
+  P.cum_valid = false;
   P.w_ready = P.idx_ready = !P.lazy;
   P.mm_valid = true;
   P.n = kept;
@@ -6626,7 +6786,8 @@ int pbx_profile_destroy(void *handle) {
                   &p->swc, &p->sbt, &p->mono, &p->bar,
                   &p->mono_trace, &p->dscal, &p->dlc, &p->pdone, &p->pstage, &p->mH,
                   &p->mhint, &p->stab, &p->srec, &p->sspec, &p->sslab, &p->sflag, &p->posst,
-                  &p->slteq, &p->mpedges, &p->meue, &p->kpos, &p->kvel, &p->rgdev};
+                  &p->slteq, &p->mpedges, &p->meue, &p->kpos, &p->kvel, &p->rgdev, &p->cxs,
+                  &p->ccum, &p->cgrid, &p->cres};
     for (Buf *b : all) b->release();
     p->pin.release();
     p->mpin.release();
@@ -6689,6 +6850,7 @@ int pbx_profile_set_level0_hint(void *handle, int enabled) {
 int pbx_profile_set_x(void *handle, const double *h_x, int64_t n) {
   return with_profile(handle, [&](Profile &P, Device &d, hipStream_t st) {
     check_n(n);
+    P.cum_valid = false;
     double *x = (double *)P.x.get(sizeof(double) * (size_t)(n ? n : 1));
     if (n) h2d_staged(d, x, h_x, sizeof(double) * n, d.stream);  // (through pinned chunks)
     P.n = n;
@@ -7012,6 +7174,7 @@ int pbx_profile_set_frame(void *handle, int flags, const double *frame) {
     if (flags & ~(PBX_FRAME_POS | PBX_FRAME_VEL | PBX_FRAME_ROT))
       fail(PBX_ERR_VALUE, "flags must be a mask of PBX_FRAME_* bits (got 0x%x)", flags);
     P.frame = frame_of(flags, frame);
+    P.cum_valid = false;
   });
 }
 
@@ -7021,6 +7184,7 @@ int pbx_profile_set_region(void *handle, int nclauses, const int *kinds, const i
                            const double *params) {
   return with_profile(handle, [&](Profile &P, Device &d, hipStream_t st) {
     P.region = region_of(nclauses, kinds, negate, params);
+    P.cum_valid = false;
     // (stream-ordered after the kernels of earlier selections that read the
     // old one; waited for, since the source is the handle's own member)
     if (P.region.any()) {
@@ -7235,6 +7399,7 @@ static int radial_equaln_entry(void *comm, void *handle, const SelectReq &q, int
     std::unique_lock<std::mutex> lk(d.mu);  // (released inside comm_allreduce's host wait)
     hipStream_t st = d.stream;
     ScopedTimer tm("pbx.profile.radial_equaln");
+    P.cum_valid = false;
     const KeyWindow kw = key_window(has_min, bin_min, has_max, bin_max);
     double *accs = (double *)P.accs.get(sizeof(double) *
                                         (size_t)std::max<int64_t>(1, stats.n * nbins * NMOM));
@@ -7333,6 +7498,109 @@ int pbx_profile_contain(void *handle, int w_src, const double *h_w, int nq, cons
     }
     PBX_HIP(hipStreamSynchronize(st));
     *denom = c[1] - c[0];
+  });
+}
+
+// ---- cumulative table (RadiusAtSurfaceDensity, properties/base.py:172-284)
+static void check_cum(const Profile &P) {
+  if (!P.cum_valid) fail(PBX_ERR_VALUE, "no cumulative table for the handle's x (pbx_profile_cum_build)");
+}
+
+// The sorted (x, cumulative weight) table of the handle's whole x:
+// pbx_profile_contain's stable value sort, then cum_table.
+int pbx_profile_cum_build(void *handle, int w_src, const double *h_w, double *r_min,
+                          double *r_max, double *total) {
+  return with_profile(handle, [&](Profile &P, Device &d, hipStream_t st) {
+    if (w_src != 1 && w_src != 2)
+      fail(PBX_ERR_VALUE, "w_src must be 1 (selection weights) or 2 (host array)");
+    if (!r_min || !r_max || !total) fail(PBX_ERR_VALUE, "null argument");
+    ScopedTimer tm("pbx.profile.cum_build");
+    const int64_t n = P.n;
+    check_n(n);
+    if (n == 0) fail(PBX_ERR_VALUE, "index 0 is out of bounds for axis 0 with size 0");
+    P.cum_valid = false;
+    const double *f = resolve_src(P, st, 0, nullptr, P.field);
+    const double *w = resolve_src(P, st, w_src, h_w, P.weight);
+    uint64_t *ka = (uint64_t *)P.pk0.get(sizeof(uint64_t) * (size_t)n);
+    uint64_t *kb = (uint64_t *)P.pk1.get(sizeof(uint64_t) * (size_t)n);
+    int32_t *va = (int32_t *)P.pv0.get(sizeof(int32_t) * (size_t)n);
+    int32_t *vb = (int32_t *)P.pv1.get(sizeof(int32_t) * (size_t)n);
+    hipLaunchKernelGGL(pct_keys, dim3(ceil_div(n, TPB)), dim3(TPB), 0, st, f, n, 0, ka);
+    for (int shift = 0; shift < 64; shift += 8) {
+      const bool last = shift + 8 >= 64;
+      prim::radix_pass<uint64_t>(P.hist, P.tsum, st, ka, shift == 0 ? nullptr : va,
+                                 shift == 0 ? VAL_IOTA : VAL_ARRAY, n, shift, last ? nullptr : kb, vb);
+      std::swap(ka, kb);
+      std::swap(va, vb);
+    }
+    double *xs = (double *)P.cxs.get(sizeof(double) * (size_t)n);
+    double *cum = (double *)P.ccum.get(sizeof(double) * (size_t)n);
+    hipLaunchKernelGGL(cum_table, dim3(1), dim3(TPB), 0, st, (const int32_t *)va, f, w, n, xs, cum);
+    PBX_HIP(hipGetLastError());
+    double h[3] = {0.0, 0.0, 0.0};  // (alive until the sync below)
+    PBX_HIP(hipMemcpyAsync(&h[0], xs, sizeof(double), hipMemcpyDeviceToHost, st));
+    PBX_HIP(hipMemcpyAsync(&h[1], xs + (n - 1), sizeof(double), hipMemcpyDeviceToHost, st));
+    PBX_HIP(hipMemcpyAsync(&h[2], cum + (n - 1), sizeof(double), hipMemcpyDeviceToHost, st));
+    PBX_HIP(hipStreamSynchronize(st));
+    *r_min = h[0];
+    *r_max = h[1];
+    *total = h[2];
+    P.cum_n = n;
+    P.cum_valid = true;
+  });
+}
+
+int pbx_profile_cum_get(void *handle, double *h_xs, double *h_cum) {
+  return with_profile(handle, [&](Profile &P, Device &d, hipStream_t st) {
+    if (!h_xs || !h_cum) fail(PBX_ERR_VALUE, "null argument");
+    check_cum(P);
+    ScopedTimer tm("pbx.profile.cum_get");
+    d2h_staged(d, h_xs, P.cxs.p, sizeof(double) * (size_t)P.cum_n, st);
+    d2h_staged(d, h_cum, P.ccum.p, sizeof(double) * (size_t)P.cum_n, st);
+    PBX_HIP(hipStreamSynchronize(st));
+  });
+}
+
+int pbx_profile_cum_sigma(void *handle, int mode, double eps, int nr, const double *h_r,
+                          double *h_sigma) {
+  return with_profile(handle, [&](Profile &P, Device &d, hipStream_t st) {
+    if (!h_r || !h_sigma) fail(PBX_ERR_VALUE, "null argument");
+    if (nr < 1 || nr > CUM_MAXGRID) fail(PBX_ERR_VALUE, "1 to %d radii per call", CUM_MAXGRID);
+    if (mode != 0 && mode != 1) fail(PBX_ERR_VALUE, "mode must be 0 (shell) or 1 (total)");
+    check_cum(P);
+    ScopedTimer tm("pbx.profile.cum_sigma");
+    double *r = (double *)P.cgrid.get(sizeof(double) * (size_t)nr);
+    double *out = (double *)P.cres.get(sizeof(double) * (size_t)std::max(nr, 8));
+    PBX_HIP(hipMemcpyAsync(r, h_r, sizeof(double) * nr, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(cum_sigma_kernel, dim3(ceil_div(nr, TPB)), dim3(TPB), 0, st,
+                       (const double *)P.cxs.p, (const double *)P.ccum.p, P.cum_n, eps, mode,
+                       (const double *)r, nr, out);
+    PBX_HIP(hipGetLastError());
+    PBX_HIP(hipMemcpyAsync(h_sigma, out, sizeof(double) * nr, hipMemcpyDeviceToHost, st));
+    PBX_HIP(hipStreamSynchronize(st));
+  });
+}
+
+int pbx_profile_cum_solve(void *handle, int mode, double eps, double target, int ngrid,
+                          const double *h_grid, double *radius, int64_t *info) {
+  return with_profile(handle, [&](Profile &P, Device &d, hipStream_t st) {
+    if (!h_grid || !radius || !info) fail(PBX_ERR_VALUE, "null argument");
+    if (ngrid < 2 || ngrid > CUM_MAXGRID) fail(PBX_ERR_VALUE, "2 to %d grid radii per call", CUM_MAXGRID);
+    if (mode != 0 && mode != 1) fail(PBX_ERR_VALUE, "mode must be 0 (shell) or 1 (total)");
+    check_cum(P);
+    ScopedTimer tm("pbx.profile.cum_solve");
+    double *grid = (double *)P.cgrid.get(sizeof(double) * (size_t)ngrid);
+    double *out = (double *)P.cres.get(sizeof(double) * (size_t)std::max(ngrid, 8));
+    PBX_HIP(hipMemcpyAsync(grid, h_grid, sizeof(double) * ngrid, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(cum_solve_kernel, dim3(1), dim3(TPB), 0, st, (const double *)P.cxs.p,
+                       (const double *)P.ccum.p, P.cum_n, eps, mode, target, (const double *)grid,
+                       ngrid, out);
+    PBX_HIP(hipGetLastError());
+    double h[5];  // (alive until the sync below)
+    PBX_HIP(hipMemcpyAsync(h, out, sizeof(h), hipMemcpyDeviceToHost, st));
+    PBX_HIP(hipStreamSynchronize(st));
+    *radius = h[0];
+    std::memcpy(info, &h[1], sizeof(int64_t) * 4);
   });
 }
 

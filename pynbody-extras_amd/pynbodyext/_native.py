@@ -167,6 +167,11 @@ _SIGNATURES: dict[str, tuple] = {
                                           POINTER(c_uint32), _dp, POINTER(c_int64), _i64p,
                                           POINTER(c_int64), _dp]),
     "pbx_profile_contain": (c_int, [c_void_p, c_int, c_void_p, c_int, _dp, _dp, _dp]),
+    "pbx_profile_cum_build": (c_int, [c_void_p, c_int, c_void_p, _dp, _dp, _dp]),
+    "pbx_profile_cum_get": (c_int, [c_void_p, _dp, _dp]),
+    "pbx_profile_cum_sigma": (c_int, [c_void_p, c_int, c_double, c_int, _dp, _dp]),
+    "pbx_profile_cum_solve": (c_int, [c_void_p, c_int, c_double, c_double, c_int, _dp, _dp,
+                                      _i64p]),
     "pbx_property_moments": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, _dp,
                                      _i64p, c_int, c_uint32, _i64p, _dp]),
     "pbx_profile_set_frame": (c_int, [c_void_p, c_int, _dp]),

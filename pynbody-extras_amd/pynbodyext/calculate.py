@@ -18,7 +18,8 @@ through, with the same names and semantics:
 * ``PropertyBase`` with ``calculate(sim, params)``, the declarative
   ``PropertyBase.dataclass`` / ``Param`` fields and host-side arithmetic
   (``+ - * /``, unary ``-``) into ``OpProperty`` / ``ConstantProperty``
-  (properties.py:125-295, fields.py:29-125, expr.py:117-260); comparisons,
+  (properties.py:125-295, fields.py:29-125, expr.py:117-260) and
+  ``_in_sim_units`` (base.py:821-848); comparisons,
   ``clip``, caching, tracing and pipelines are not provided.
 
 MI355X addition: a calculator may implement ``execute_fused(ctx, input,
@@ -572,6 +573,34 @@ class PropertyBase(_Arithmetic, CalculatorBase):
         if spec is None:
             return NotImplemented
         return self._device_route(ctx, input, spec)
+
+    def _in_sim_units(self, value, sim_parameter: str, sim, target_units=None) -> float:
+        """``value`` as a float in ``target_units`` (default: the units of
+        ``sim[sim_parameter]``) — reference core/calculate/base.py:821-848.
+        Numbers pass through, one-element arrays go through ``.item()``,
+        ``SimArray`` and unit strings / objects are converted first."""
+        from ._pyn import SimArray
+        from ._pyn import units as _units
+
+        target_unit = _units.Unit(target_units) if target_units is not None \
+            else sim[sim_parameter].units
+        context = sim.conversion_context() if hasattr(sim, "conversion_context") else {}
+        if isinstance(value, str):
+            value = _units.Unit(value)
+        if isinstance(value, _units.UnitBase):
+            value = float(value.in_units(target_unit, **context)) if hasattr(value, "in_units") \
+                else float(value.ratio(target_unit))
+        if isinstance(value, np.ndarray):
+            if value.ndim == 0 or value.size == 1:
+                if isinstance(value, SimArray):
+                    value = value.in_units(target_unit, **context).item()
+                else:
+                    value = value.item()
+            else:
+                raise TypeError(f"value must be scalar-like, got shape {value.shape}")
+        if isinstance(value, (int, float)):
+            return float(value)
+        raise TypeError(f"unsupported value type: {type(value)!r}")
 
     __hash__ = object.__hash__
 

@@ -3,7 +3,11 @@
 Thin ctypes wrapper of the pbx_profile_* entry points (include/pbx.h):
 the binned quantity x (and, after a fused selection, the selection mass
 and original indices) stays in HBM; edges, counts, CSR and per-bin sums are
-computed by the HIP kernels of csrc/profile.hip.
+computed by the HIP kernels of csrc/profile.hip.  So is the cumulative table
+of the whole x (``cum_build``: x in stable value order with the cumulative
+weights, kept on the handle) with the surface density read off it
+(``cum_sigma``) and the scan-and-bisect solve of RadiusAtSurfaceDensity
+(``cum_solve``: one launch, one read-back).
 """
 from __future__ import annotations
 
@@ -539,6 +543,56 @@ class DeviceBins:
         nat.call("pbx_profile_contain", self._h, ws, self._ptr(wa), qa.shape[0], nat.dptr(qa),
                  nat.dptr(out), byref(denom))
         return out, denom.value
+
+    # -- cumulative table (RadiusAtSurfaceDensity) ---------------------------
+    def cum_build(self, weights=SRC_W) -> tuple[float, float, float]:
+        """(r_min, r_max, total): build the handle's table of its WHOLE x in
+        stable value order with the cumulative weights in that order
+        (np.sort / np.cumsum bit for bit; pbx_profile_cum_build).  weights:
+        SRC_W (the selection's) or a host array of length n.  The table
+        stays on the handle until its x is replaced (a new selection,
+        ``set_x``, a new frame or region)."""
+        ws, wa = self._src(weights)
+        lo, hi, tot = c_double(), c_double(), c_double()
+        nat.call("pbx_profile_cum_build", self._h, ws, self._ptr(wa), byref(lo), byref(hi),
+                 byref(tot))
+        return lo.value, hi.value, tot.value
+
+    def cum_table(self) -> tuple[np.ndarray, np.ndarray]:
+        """(sorted x, cumulative weights) of ``cum_build``, read back."""
+        xs, cum = np.empty(self.n), np.empty(self.n)
+        nat.call("pbx_profile_cum_get", self._h, nat.dptr(xs), nat.dptr(cum))
+        return xs, cum
+
+    @staticmethod
+    def _cum_mode(mode) -> int:
+        # (the reference treats every mode string but "total" as the shell)
+        return int(mode) if isinstance(mode, (int, np.integer)) else int(mode == "total")
+
+    def cum_sigma(self, r, mode="shell", eps: float = 0.01) -> np.ndarray:
+        """The surface density at the radii ``r`` (at most 4096) read off the
+        table: the reference's ``_sigma_at_radius`` with product squares
+        (pbx_profile_cum_sigma).  mode: "total", anything else the shell of
+        width eps (or the library's code, 1 / 0)."""
+        ra = np.ascontiguousarray(np.atleast_1d(np.asarray(r, dtype=np.float64)))
+        out = np.empty(ra.shape[0])
+        nat.call("pbx_profile_cum_sigma", self._h, self._cum_mode(mode), float(eps), ra.shape[0],
+                 nat.dptr(ra), nat.dptr(out))
+        return out
+
+    def cum_solve(self, target: float, grid, mode="shell",
+                  eps: float = 0.01) -> tuple[float, np.ndarray]:
+        """(radius, info): the first sign change of sigma - target along
+        ``grid`` (2 to 4096 radii) and the reference's 80-step bisection in
+        it, one launch and one read-back (pbx_profile_cum_solve).  info =
+        [status (0 solved, 1 not bracketed: radius NaN), bracket index,
+        iterations run, 1 if the loop stopped early]."""
+        ga = np.ascontiguousarray(np.asarray(grid, dtype=np.float64).reshape(-1))
+        radius = c_double()
+        info = np.zeros(4, dtype=np.int64)
+        nat.call("pbx_profile_cum_solve", self._h, self._cum_mode(mode), float(eps), float(target),
+                 ga.shape[0], nat.dptr(ga), byref(radius), _i64(info))
+        return radius.value, info
 
     def moments(self, field=SRC_X, weights=SRC_NONE, cols: int = ALL_COLS) -> np.ndarray:
         """Per-bin sums (nbins, 7): Σw, Σf·w, Σf²·w, Σf, Σf², Σ|f|·w, Σ|f|.

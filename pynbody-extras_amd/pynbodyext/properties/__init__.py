@@ -5,6 +5,7 @@ from .base import (
     ParameterContain,
     ParamSum,
     PropertyBase,
+    RadiusAtSurfaceDensity,
     SurfaceDensity,
     VolumeDensity,
 )
@@ -17,6 +18,7 @@ __all__ = [
     "ParameterContain",
     "VolumeDensity",
     "SurfaceDensity",
+    "RadiusAtSurfaceDensity",
     "KappaRot",
     "KappaRotMean",
     "CenPos",
