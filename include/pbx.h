@@ -710,6 +710,91 @@ int pbx_property_shrink_center(const double *pos, const double *mass, int64_t n,
                                const int64_t *fam, int nfam, double r0, double shrink_factor,
                                int64_t min_particles, double *h_cen, int64_t *iterations,
                                int64_t *n_last);
+/* Enclosed mass at many radii in one streaming pass: what the bisection of
+ * a virial radius asks of the particles (pynbody analysis.halo.virial_radius:
+ * M(<r) = dot(mass, r_arr < r)), and the extrema VirialRadius and SpinParam
+ * start from (x.max() - x.min(), r.max()).  Stateless; pos / mass, on_device,
+ * the sphere, the families, flags / frame and the region clauses as in
+ * pbx_property_moments_region, with the same meaning: a particle is kept as
+ * that pass keeps it, and x, y, z below are the frame's coordinates.  Per
+ * kept particle, without FMA contraction, with a correctly rounded sqrt and
+ * m = mass (1.0 when mass is NULL):
+ *   r = sqrt((x*x + y*y) + z*z)
+ *   h_msum[j]  = sum of m over the kept particles with r < h_t[j]   (strict)
+ *   h_count[j] = the number of those particles
+ * for j < nt, 0 <= nt <= PBX_ENCLOSED_MAX; a NaN r or a NaN h_t[j] enters no
+ * sum.  nt == 0: only the extrema and *n_kept (h_t, h_msum and h_count may be
+ * NULL).  h_ext[PBX_ENCLOSED_NEXT] (NULL: not wanted) = min x, max x, min y,
+ * max y, min z, max z, max r over the kept particles; a NaN among them makes
+ * that extremum NaN, as numpy's min / max do; nothing kept: all seven NaN,
+ * the sums 0.0.  *n_kept = the number of kept particles.  The thresholds sit
+ * in registers, so they cost arithmetic and no bandwidth: the pass reads 32
+ * bytes per particle whatever nt is.  (The device compares r*r with the
+ * smallest double whose correctly rounded sqrt reaches h_t[j], found on the
+ * host: sqrt is monotonic, so every particle is decided as r < h_t[j]
+ * decides it, and max r is the sqrt of max r*r.)
+ * No atomics: the order of summation is fixed by the particle count alone,
+ * and every threshold has an accumulator of its own.  Two contracts follow:
+ *   1. the bits of h_msum[j] depend on the particles, the scope and h_t[j]
+ *      only;
+ *   2. they do not depend on nt, on the other thresholds, on the position
+ *      of h_t[j] in the list, or on whether the extrema are wanted.
+ * So a batch of thresholds stands for as many single evaluations.  The
+ * order is moreover that of the PBX_PROP_MASS sum of the pass above: on
+ * the same n particles with m replaced by 0.0 wherever the particle is not
+ * kept or r < h_t[j] fails, that pass returns the bits of h_msum[j].
+ * PBX_ERR_VALUE: nt outside [0, PBX_ENCLOSED_MAX], a needed array NULL,
+ * pos NULL, n < 0, nfam > 16, a bad frame or region. */
+#define PBX_ENCLOSED_MAX 31
+#define PBX_ENCLOSED_NEXT 7
+int pbx_property_enclosed(const double *pos, const double *mass, int64_t n, int on_device,
+                          int use_sphere, const double *sphere, const int64_t *fam, int nfam,
+                          int flags, const double *frame, int nclauses, const int *kinds,
+                          const int *negate, const double *params, int nt, const double *h_t,
+                          int64_t *n_kept, double *h_msum, int64_t *h_count, double *h_ext);
+/* The virial radius of the kept particles: the radius at which the mean
+ * enclosed density M(<r) / (4 pi r^3 / 3) equals target_rho, by the bisection
+ * of pynbody's analysis.halo.virial_radius (util.bisect with epsilon = 0).
+ * The scope arguments are those of the enclosed pass.  The particles are
+ * staged once (or borrowed, on_device = 1) and the enclosed pass runs over
+ * them, one read-back per pass.  Without has_rmax, r_max = max x - min x of
+ * the kept particles, from one extrema pass (nt = 0).  The loop, in host
+ * doubles, pow being libm's:
+ *   left = 0.0; right = r_max
+ *   for i in 0 .. niter_max - 1:
+ *     if (right - left) < 0: return (right + left) / 2
+ *     mid = (left + right) / 2
+ *     z = target_rho - M(<mid) / (4 * pi * pow(mid, 3.0) / 3)
+ *     if fabs(z) < eta: return mid
+ *     else if z < 0: left = mid
+ *     else: right = mid
+ *   not converged
+ * A pass evaluates the 2^L - 1 midpoints the next L iterations can reach,
+ * each computed by the same (left + right) / 2 from the bounds its branch
+ * would hold, so it is the value the loop would reach; the decisions are
+ * then walked on the host (contracts 1 and 2 above: the result does not
+ * depend on L).  levels = L, 1 <= L <= PBX_ENCLOSED_LEVELS; 0: the
+ * library's choice (PBX_VIRIAL_LEVELS).  *h_radius = the loop's return value
+ * (NaN when not converged); *iterations = the midpoints the loop evaluated
+ * (niter_max when not converged); *passes = the enclosed passes, the
+ * extrema pass included; *n_kept = the kept particles; *status =
+ * PBX_VIRIAL_CONVERGED or PBX_VIRIAL_NOT_CONVERGED, the latter with PBX_OK:
+ * it is a result, not an error.  Nothing kept and no r_max: r_max is NaN and
+ * the loop cannot converge; that result is returned after the extrema pass.
+ * PBX_ERR_VALUE: target_rho NaN or <= 0, eta NaN or < 0, niter_max < 1,
+ * levels outside [0, PBX_ENCLOSED_LEVELS], and what the enclosed pass
+ * rejects. */
+#define PBX_ENCLOSED_LEVELS 5
+#define PBX_VIRIAL_LEVELS 4
+#define PBX_VIRIAL_CONVERGED 0
+#define PBX_VIRIAL_NOT_CONVERGED 1
+int pbx_property_virial_radius(const double *pos, const double *mass, int64_t n, int on_device,
+                               int use_sphere, const double *sphere, const int64_t *fam, int nfam,
+                               int flags, const double *frame, int nclauses, const int *kinds,
+                               const int *negate, const double *params, double target_rho,
+                               double eta, int niter_max, int has_rmax, double r_max, int levels,
+                               double *h_radius, int64_t *iterations, int64_t *passes,
+                               int64_t *n_kept, int *status);
 
 /* ------------------------------------------------------------------ */
 /* multi-GPU: RCCL communicator (one process per GPU, over xGMI)       */

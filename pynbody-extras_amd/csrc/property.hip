@@ -245,6 +245,252 @@ __global__ void __launch_bounds__(PROP_RG *PROP_NOUT)
   }
 }
 
+// --------------------------------------------------------- enclosed sums
+// pbx_property_enclosed: Σ m and the count of the kept particles with
+// r < t[j] for up to ENC_MAX thresholds, and the extrema of x, y, z, r, in
+// one read of pos / mass (32 bytes per particle whatever the number of
+// thresholds: they are kernel arguments, their accumulators registers).  No
+// sqrt is taken on the device: the host turns a threshold t into the exact
+// bound on the squared radius (enc_square_bound).  The grid, the particle -> thread mapping, the order in which a thread adds and
+// the three reduction steps are those of property_moments / property_reduce,
+// so a threshold's sum has the bits of that pass's mass sum over the same n
+// particles with the masses outside the threshold replaced by 0.0.
+constexpr int ENC_MAX = PBX_ENCLOSED_MAX;    // thresholds of one pass
+constexpr int ENC_NEXT = PBX_ENCLOSED_NEXT;  // min x, max x, min y, max y, min z, max z, max r
+constexpr int ENC_NCNT = ENC_MAX + 1;        // the thresholds' counts, then the kept count
+constexpr int ENC_RCOLS = 32;                // columns of enclosed_reduce (>= ENC_NCNT)
+constexpr int ENC_NOUT = ENC_MAX + ENC_NEXT + ENC_NCNT;  // 8-byte words of a result
+static_assert(ENC_NCNT <= ENC_RCOLS && ENC_NEXT <= ENC_RCOLS, "enclosed_reduce columns");
+static_assert(64 + ENC_NCNT <= 128 && 128 + ENC_NEXT <= PROP_TPB, "writer threads of a block");
+
+template <int NTC>
+struct EncThresholds {
+  double t[NTC];  // (unused slots NaN: nothing is below them)
+};
+
+// the rows of partials of one pass (a row per block) and its result
+struct EncPart {
+  double *sum;     // [PROP_MAX_BLOCKS][ENC_MAX]
+  double *ext;     // [PROP_MAX_BLOCKS][ENC_NEXT]
+  long long *cnt;  // [PROP_MAX_BLOCKS][ENC_NCNT]
+};
+
+// numpy's min / max of two values: a NaN wins (and stays)
+__device__ __forceinline__ double enc_min(double a, double v) { return (v < a || v != v) ? v : a; }
+__device__ __forceinline__ double enc_max(double a, double v) { return (v > a || v != v) ? v : a; }
+__device__ __forceinline__ double enc_fold(int col, double a, double v) {
+  return (col < 6 && !(col & 1)) ? enc_min(a, v) : enc_max(a, v);
+}
+__device__ __forceinline__ double enc_identity(int col) {
+  return (col < 6 && !(col & 1)) ? __builtin_inf() : -__builtin_inf();
+}
+
+// NTC: the thresholds the instantiation holds (nt rounded up to 2^L - 1).
+// FRAME / REGION as in property_moments.  want_ext (uniform): the extrema.
+template <int NTC, bool FRAME, bool REGION>
+__global__ void __launch_bounds__(PROP_TPB)
+    property_enclosed(const double *__restrict__ pos, const double *__restrict__ mass, PropParams p,
+                      Frame fr, Region rg, EncThresholds<NTC> th, int want_ext, EncPart out) {
+#pragma clang fp contract(off)
+  __shared__ double ws[PROP_NW][NTC];
+  __shared__ long long wc[PROP_NW][NTC + 1];
+  __shared__ double we[PROP_NW][ENC_NEXT];
+  double acc[NTC];
+  unsigned cn[NTC];  // (a thread sees span / (grid * PROP_TPB) particles: 32 bits hold it)
+#pragma unroll
+  for (int j = 0; j < NTC; ++j) {
+    acc[j] = 0.0;
+    cn[j] = 0;
+  }
+  unsigned c = 0;
+  double ex[ENC_NEXT];
+#pragma unroll
+  for (int e = 0; e < ENC_NEXT; ++e) ex[e] = enc_identity(e);
+  const int64_t stride = (int64_t)gridDim.x * PROP_TPB;
+  for (int64_t j0 = (int64_t)blockIdx.x * PROP_TPB + threadIdx.x; j0 < p.span;
+       j0 += stride * PROP_ITEMS) {
+    double x[PROP_ITEMS], y[PROP_ITEMS], z[PROP_ITEMS], m[PROP_ITEMS];
+    bool keep[PROP_ITEMS];
+    // (as property_moments: every load of the sweep in flight, an unkept
+    // particle reads particle 0 of the span)
+#pragma unroll
+    for (int k = 0; k < PROP_ITEMS; ++k) {
+      const int64_t j = j0 + k * stride;
+      keep[k] = (j < p.span) && prop_in_family(p.base + j, p);
+      const double *q = pos + 3 * (keep[k] ? j : 0);
+      x[k] = q[0];
+      y[k] = q[1];
+      z[k] = q[2];
+    }
+    if constexpr (FRAME) {
+#pragma unroll
+      for (int k = 0; k < PROP_ITEMS; ++k) frame_apply(fr.pos, x[k], y[k], z[k]);
+    }
+    if (p.use_sphere) {
+#pragma unroll
+      for (int k = 0; k < PROP_ITEMS; ++k) keep[k] = keep[k] && prop_in_sphere(x[k], y[k], z[k], p);
+    }
+    if constexpr (REGION) {
+#pragma unroll
+      for (int k = 0; k < PROP_ITEMS; ++k) keep[k] = keep[k] & region_keep(rg, x[k], y[k], z[k]);
+    }
+#pragma unroll
+    for (int k = 0; k < PROP_ITEMS; ++k) {
+      m[k] = 1.0;
+      if (mass && keep[k]) m[k] = mass[j0 + k * stride];
+    }
+    // The squared radius only: th.t[j] is the smallest double whose correctly
+    // rounded sqrt reaches the caller's threshold (enc_square_bound), so
+    // r2 < th.t[j] is sqrt(r2) < threshold exactly, and max r is the sqrt of
+    // max r2 (the host takes it).  Everything below is predicated, not
+    // branched.
+    double r2[PROP_ITEMS];
+#pragma unroll
+    for (int k = 0; k < PROP_ITEMS; ++k) {
+      r2[k] = (x[k] * x[k] + y[k] * y[k]) + z[k] * z[k];
+      c += keep[k];
+    }
+    // (threshold by threshold: an accumulator still adds its particles in
+    // index order, and a threshold is live for four compares only)
+#pragma unroll
+    for (int j = 0; j < NTC; ++j) {
+      const double tj = th.t[j];
+#pragma unroll
+      for (int k = 0; k < PROP_ITEMS; ++k) {
+        const bool in = keep[k] & (r2[k] < tj);  // (a NaN on either side: false)
+        acc[j] = acc[j] + (in ? m[k] : 0.0);
+        cn[j] += in;
+      }
+    }
+    if (want_ext) {
+#pragma unroll
+      for (int k = 0; k < PROP_ITEMS; ++k) {
+        const bool kp = keep[k];
+        ex[0] = kp ? enc_min(ex[0], x[k]) : ex[0];
+        ex[1] = kp ? enc_max(ex[1], x[k]) : ex[1];
+        ex[2] = kp ? enc_min(ex[2], y[k]) : ex[2];
+        ex[3] = kp ? enc_max(ex[3], y[k]) : ex[3];
+        ex[4] = kp ? enc_min(ex[4], z[k]) : ex[4];
+        ex[5] = kp ? enc_max(ex[5], z[k]) : ex[5];
+        ex[6] = kp ? enc_max(ex[6], r2[k]) : ex[6];
+      }
+    }
+  }
+  // lanes of a wave: the xor butterfly of property_moments
+  // (a wave's counts still fit 32 bits)
+#pragma unroll
+  for (int j = 0; j < NTC; ++j) {
+    double v = acc[j];
+    unsigned u = cn[j];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      v = v + __shfl_xor(v, o, 64);
+      u = u + __shfl_xor(u, o, 64);
+    }
+    acc[j] = v;
+    cn[j] = u;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) c = c + __shfl_xor(c, o, 64);
+  if (want_ext) {
+#pragma unroll
+    for (int e = 0; e < ENC_NEXT; ++e) {
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) ex[e] = enc_fold(e, ex[e], __shfl_xor(ex[e], o, 64));
+    }
+  }
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  if (lane == 0) {
+#pragma unroll
+    for (int j = 0; j < NTC; ++j) ws[w][j] = acc[j];
+#pragma unroll
+    for (int j = 0; j < NTC; ++j) wc[w][j] = cn[j];
+    wc[w][NTC] = c;
+#pragma unroll
+    for (int e = 0; e < ENC_NEXT; ++e) we[w][e] = ex[e];
+  }
+  __syncthreads();
+  // waves of the block, in wave order: sums by the first wave's threads,
+  // counts by the second's, extrema by the third's
+  const int t = threadIdx.x;
+  if (t < NTC) {
+    double s = ws[0][t];
+    for (int ww = 1; ww < PROP_NW; ++ww) s = s + ws[ww][t];
+    out.sum[(int64_t)blockIdx.x * ENC_MAX + t] = s;
+  } else if (t >= 64 && t < 64 + NTC + 1) {
+    const int j = t - 64;
+    long long s = 0;
+    for (int ww = 0; ww < PROP_NW; ++ww) s += wc[ww][j];
+    // (the kept count sits in the last column whatever NTC is)
+    out.cnt[(int64_t)blockIdx.x * ENC_NCNT + (j == NTC ? ENC_MAX : j)] = s;
+  } else if (want_ext && t >= 128 && t < 128 + ENC_NEXT) {
+    const int e = t - 128;
+    double s = we[0][e];
+    for (int ww = 1; ww < PROP_NW; ++ww) s = enc_fold(e, s, we[ww][e]);
+    out.ext[(int64_t)blockIdx.x * ENC_NEXT + e] = s;
+  }
+}
+
+// The rows of an enclosed pass in the order of property_reduce: partial g =
+// rows g, g + PROP_RG, ... in turn, then the partials in g order.  res:
+// ENC_MAX sums, ENC_NEXT extrema, ENC_NCNT counts (columns >= nt untouched).
+// Blocks of PROP_RG * ENC_RCOLS threads: block 0 folds the sums, block 1 the
+// counts, block 2 (launched only when they are wanted) the extrema.  A thread
+// has all of its at most ENC_RPT rows in flight before it folds them in row
+// order: one load latency, not one per row.
+constexpr int ENC_RPT = PROP_MAX_BLOCKS / PROP_RG;  // rows of one partial
+
+template <class T, class Fold>
+__device__ __forceinline__ T enc_fold_rows(const T *__restrict__ col0, int stride, int g, int rows,
+                                           T init, Fold fold) {
+  T v[ENC_RPT];
+#pragma unroll
+  for (int i = 0; i < ENC_RPT; ++i) {
+    const int r = g + i * PROP_RG;
+    v[i] = col0[(int64_t)(r < rows ? r : 0) * stride];
+  }
+  T s = init;
+#pragma unroll
+  for (int i = 0; i < ENC_RPT; ++i)
+    if (g + i * PROP_RG < rows) s = fold(s, v[i]);
+  return s;
+}
+
+__global__ void __launch_bounds__(PROP_RG *ENC_RCOLS)
+    enclosed_reduce(EncPart part, int rows, int nt, double *__restrict__ res) {
+  __shared__ double gd[PROP_RG][ENC_RCOLS];
+  __shared__ long long gc[PROP_RG][ENC_RCOLS];
+  const int g = threadIdx.x / ENC_RCOLS, col = threadIdx.x % ENC_RCOLS;
+  const auto add = [](double a, double b) { return a + b; };
+  if (blockIdx.x == 0) {  // the sums
+    if (col < nt) gd[g][col] = enc_fold_rows(part.sum + col, ENC_MAX, g, rows, 0.0, add);
+    __syncthreads();
+    if (g != 0 || col >= nt) return;
+    double s = 0.0;
+    for (int k = 0; k < PROP_RG; ++k) s = s + gd[k][col];
+    res[col] = s;
+  } else if (blockIdx.x == 1) {  // the thresholds' counts and the kept count
+    const bool has = col < nt || col == ENC_MAX;
+    if (has)
+      gc[g][col] = enc_fold_rows(part.cnt + col, ENC_NCNT, g, rows, 0ll,
+                                 [](long long a, long long b) { return a + b; });
+    __syncthreads();
+    if (g != 0 || !has) return;
+    long long s = 0;
+    for (int k = 0; k < PROP_RG; ++k) s += gc[k][col];
+    ((long long *)res)[ENC_MAX + ENC_NEXT + col] = s;
+  } else {  // the extrema
+    const bool has = col < ENC_NEXT;
+    const auto fold = [col](double a, double b) { return enc_fold(col, a, b); };
+    if (has) gd[g][col] = enc_fold_rows(part.ext + col, ENC_NEXT, g, rows, enc_identity(col), fold);
+    __syncthreads();
+    if (g != 0 || !has) return;
+    double s = enc_identity(col);
+    for (int k = 0; k < PROP_RG; ++k) s = enc_fold(col, s, gd[k][col]);
+    res[ENC_MAX + col] = s;
+  }
+}
+
 // ------------------------------------------------------------------- host
 // blocks of a pass over `span` particles (a function of span alone)
 static int grid_of(int64_t span) {
@@ -362,6 +608,127 @@ static void run_pass(Device &d, hipStream_t st, const Staged &s, uint32_t groups
   std::memcpy(n_kept, &h[NS], sizeof(int64_t));
 }
 
+// what one enclosed pass returns (entries >= nt are not meaningful)
+struct Enclosed {
+  int64_t kept = 0;
+  double msum[ENC_MAX];
+  int64_t count[ENC_MAX];
+  double ext[ENC_NEXT];
+};
+
+// The smallest double s >= +0 with sqrt(s) >= t (NaN for a NaN t; +0 for
+// t <= 0: nothing is below it).  The correctly rounded sqrt is monotonic, so
+// the s with sqrt(s) >= t are exactly those from this one up, and
+// sqrt(r2) < t  <=>  r2 < enc_square_bound(t): the kernel takes no sqrt and
+// decides every particle as the definition in pbx.h does.  Bisection over
+// the bit patterns of the non-negative doubles, which order as their values.
+static double enc_square_bound(double t) {
+  if (t != t) return t;
+  auto at = [](uint64_t b) {
+    double v;
+    std::memcpy(&v, &b, sizeof(v));
+    return v;
+  };
+  uint64_t lo = 0, hi = 0x7ff0000000000000ull;  // +0 .. +inf
+  if (std::sqrt(at(lo)) >= t) return 0.0;
+  while (hi - lo > 1) {  // sqrt(at(lo)) < t <= sqrt(at(hi))
+    const uint64_t mid = lo + (hi - lo) / 2;
+    if (std::sqrt(at(mid)) >= t) hi = mid;
+    else lo = mid;
+  }
+  return at(hi);
+}
+
+template <int NTC>
+static void launch_enclosed(hipStream_t st, int grid, const Staged &s, int nt, const double *t,
+                            int want_ext, const EncPart &part) {
+  EncThresholds<NTC> th;
+  for (int j = 0; j < NTC; ++j) th.t[j] = j < nt ? enc_square_bound(t[j]) : __builtin_nan("");
+  auto launch = [&](auto kern) {
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(PROP_TPB), 0, st, s.pos, s.mass, s.p, s.fr, s.rg, th,
+                       want_ext, part);
+  };
+  const bool framed = s.fr.pos.shift || s.fr.pos.rot;
+  if (s.rg.any()) {
+    if (framed) launch(property_enclosed<NTC, true, true>);
+    else launch(property_enclosed<NTC, false, true>);
+  } else if (framed) launch(property_enclosed<NTC, true, false>);
+  else launch(property_enclosed<NTC, false, false>);
+}
+
+// one enclosed pass + its reduction + the read-back (one stream sync)
+static void run_enclosed(Device &d, hipStream_t st, const Staged &s, int nt, const double *t,
+                         bool want_ext, Enclosed &e) {
+  e.kept = 0;
+  for (int j = 0; j < ENC_MAX; ++j) {
+    e.msum[j] = 0.0;
+    e.count[j] = 0;
+  }
+  for (int k = 0; k < ENC_NEXT; ++k) e.ext[k] = __builtin_nan("");
+  if (s.p.span <= 0) return;
+  const int grid = grid_of(s.p.span);
+  // [rows of sums][rows of extrema][rows of counts][the result]
+  const size_t rows = PROP_MAX_BLOCKS;
+  double *base = (double *)d.slot(kSlotPropPart)
+                     .ensure(sizeof(double) * (rows * (ENC_MAX + ENC_NEXT + ENC_NCNT) + ENC_NOUT));
+  EncPart part;
+  part.sum = base;
+  part.ext = part.sum + rows * ENC_MAX;
+  part.cnt = (long long *)(part.ext + rows * ENC_NEXT);
+  double *res = (double *)(part.cnt + rows * ENC_NCNT);
+  // the instantiation that holds nt thresholds: 2^L - 1 of them
+  if (nt <= 1) launch_enclosed<1>(st, grid, s, nt, t, want_ext, part);
+  else if (nt <= 3) launch_enclosed<3>(st, grid, s, nt, t, want_ext, part);
+  else if (nt <= 7) launch_enclosed<7>(st, grid, s, nt, t, want_ext, part);
+  else if (nt <= 15) launch_enclosed<15>(st, grid, s, nt, t, want_ext, part);
+  else launch_enclosed<ENC_MAX>(st, grid, s, nt, t, want_ext, part);
+  PBX_HIP(hipGetLastError());
+  // (blocks: the sums, the counts and, when wanted, the extrema)
+  hipLaunchKernelGGL(enclosed_reduce, dim3(want_ext ? 3 : 2), dim3(PROP_RG * ENC_RCOLS), 0, st,
+                     part, grid, nt, res);
+  PBX_HIP(hipGetLastError());
+  double h[ENC_NOUT];
+  PBX_HIP(hipMemcpyAsync(h, res, sizeof(h), hipMemcpyDeviceToHost, st));
+  PBX_HIP(hipStreamSynchronize(st));
+  const int64_t *hc = (const int64_t *)(h + ENC_MAX + ENC_NEXT);
+  e.kept = hc[ENC_MAX];
+  for (int j = 0; j < nt; ++j) {
+    e.msum[j] = h[j];
+    e.count[j] = hc[j];
+  }
+  if (want_ext && e.kept > 0) {
+    for (int k = 0; k < ENC_NEXT; ++k) e.ext[k] = h[ENC_MAX + k];
+    e.ext[6] = std::sqrt(e.ext[6]);  // (max r = sqrt(max r2): sqrt is monotonic; a NaN stays)
+  }
+}
+
+// the arguments the two enclosed entry points share, checked and staged
+static Staged stage_scope(Device &d, hipStream_t st, const double *pos, const double *mass,
+                          int64_t n, int on_device, int use_sphere, const double *sphere,
+                          const int64_t *fam, int nfam, int flags, const double *frame,
+                          const Region &rg) {
+  Staged s = stage_particles(d, st, pos, nullptr, mass, n, on_device, fam, nfam);
+  if (use_sphere) {
+    s.p.use_sphere = 1;
+    s.p.cx = sphere[0];
+    s.p.cy = sphere[1];
+    s.p.cz = sphere[2];
+    s.p.r2max = sphere[3];
+  }
+  s.fr = frame_of(flags, frame);
+  s.rg = rg;
+  return s;
+}
+
+static void check_scope(const double *pos, int64_t n, int use_sphere, const double *sphere,
+                        const int64_t *fam, int nfam, int flags) {
+  if (flags & ~(PBX_FRAME_POS | PBX_FRAME_VEL | PBX_FRAME_ROT))
+    fail(PBX_ERR_VALUE, "flags must be a mask of PBX_FRAME_* bits (got 0x%x)", flags);
+  check_common(n, fam, nfam);
+  if (use_sphere && !sphere) fail(PBX_ERR_VALUE, "use_sphere without a sphere");
+  if (!pos) fail(PBX_ERR_VALUE, "pos is NULL");
+}
+
 }  // namespace prop
 }  // namespace pbx
 
@@ -472,6 +839,141 @@ int pbx_property_shrink_center(const double *pos, const double *mass, int64_t n,
     for (int k = 0; k < 3; ++k) h_cen[k] = com[k];
     *iterations = it;
     *n_last = last;
+  });
+}
+
+int pbx_property_enclosed(const double *pos, const double *mass, int64_t n, int on_device,
+                          int use_sphere, const double *sphere, const int64_t *fam, int nfam,
+                          int flags, const double *frame, int nclauses, const int *kinds,
+                          const int *negate, const double *params, int nt, const double *h_t,
+                          int64_t *n_kept, double *h_msum, int64_t *h_count, double *h_ext) {
+  return guard([&] {
+    const Region rg = region_of(nclauses, kinds, negate, params);
+    if (!n_kept) fail(PBX_ERR_VALUE, "null output");
+    if (nt < 0 || nt > ENC_MAX)
+      fail(PBX_ERR_VALUE, "nt must lie in [0, %d] (got %d)", ENC_MAX, nt);
+    if (nt > 0 && (!h_t || !h_msum || !h_count))
+      fail(PBX_ERR_VALUE, "thresholds without h_t, h_msum or h_count");
+    check_scope(pos, n, use_sphere, sphere, fam, nfam, flags);
+    Device &d = current_device();
+    std::lock_guard<std::mutex> lk(d.mu);
+    hipStream_t st = d.stream;
+    ScopedTimer tm("pbx.property.enclosed");
+    const Staged s = stage_scope(d, st, pos, mass, n, on_device, use_sphere, sphere, fam, nfam,
+                                 flags, frame, rg);
+    Enclosed e;
+    run_enclosed(d, st, s, nt, h_t, h_ext != nullptr, e);
+    *n_kept = e.kept;
+    for (int j = 0; j < nt; ++j) {
+      h_msum[j] = e.msum[j];
+      h_count[j] = e.count[j];
+    }
+    if (h_ext)
+      for (int k = 0; k < ENC_NEXT; ++k) h_ext[k] = e.ext[k];
+  });
+}
+
+int pbx_property_virial_radius(const double *pos, const double *mass, int64_t n, int on_device,
+                               int use_sphere, const double *sphere, const int64_t *fam, int nfam,
+                               int flags, const double *frame, int nclauses, const int *kinds,
+                               const int *negate, const double *params, double target_rho,
+                               double eta, int niter_max, int has_rmax, double r_max, int levels,
+                               double *h_radius, int64_t *iterations, int64_t *passes,
+                               int64_t *n_kept, int *status) {
+  return guard([&] {
+    const Region rg = region_of(nclauses, kinds, negate, params);
+    if (!h_radius || !iterations || !passes || !n_kept || !status)
+      fail(PBX_ERR_VALUE, "null output");
+    if (!(target_rho > 0.0)) fail(PBX_ERR_VALUE, "target_rho must be positive (got %g)", target_rho);
+    if (!(eta >= 0.0)) fail(PBX_ERR_VALUE, "eta must not be negative (got %g)", eta);
+    if (niter_max < 1) fail(PBX_ERR_VALUE, "niter_max must be >= 1 (got %d)", niter_max);
+    if (levels < 0 || levels > PBX_ENCLOSED_LEVELS)
+      fail(PBX_ERR_VALUE, "levels must lie in [0, %d] (got %d)", PBX_ENCLOSED_LEVELS, levels);
+    check_scope(pos, n, use_sphere, sphere, fam, nfam, flags);
+    Device &d = current_device();
+    std::lock_guard<std::mutex> lk(d.mu);
+    hipStream_t st = d.stream;
+    ScopedTimer tm("pbx.property.virial_radius");
+    // staged once; every pass re-reads them from HBM
+    const Staged s = stage_scope(d, st, pos, mass, n, on_device, use_sphere, sphere, fam, nfam,
+                                 flags, frame, rg);
+    const int L = levels ? levels : PBX_VIRIAL_LEVELS;
+    Enclosed e;
+    int64_t np = 0;
+    *h_radius = __builtin_nan("");
+    *status = PBX_VIRIAL_NOT_CONVERGED;
+    *iterations = niter_max;
+    *n_kept = 0;
+    if (!has_rmax) {
+      run_enclosed(d, st, s, 0, nullptr, true, e);
+      ++np;
+      r_max = e.ext[1] - e.ext[0];
+      *n_kept = e.kept;
+      if (e.kept == 0) {  // (r_max is NaN: every mid and every z is, nothing converges)
+        *passes = np;
+        return;
+      }
+    }
+    const double pi = 3.141592653589793;
+    double left = 0.0, right = r_max;
+    int i = 0;
+    while (i < niter_max) {
+      if ((right - left) < 0) {
+        *h_radius = (right + left) / 2;
+        *status = PBX_VIRIAL_CONVERGED;
+        *iterations = i;
+        break;
+      }
+      // the midpoints of the next lv iterations in heap order: node k holds
+      // the bounds its branch would; child 2k + 1 follows left = mid, child
+      // 2k + 2 follows right = mid
+      const int lv = std::min(L, niter_max - i);
+      const int nt = (1 << lv) - 1;
+      double lo[ENC_MAX], hi[ENC_MAX], t[ENC_MAX];
+      lo[0] = left;
+      hi[0] = right;
+      for (int k = 0; k < nt; ++k) {
+        t[k] = (lo[k] + hi[k]) / 2;
+        if (2 * k + 2 < nt) {
+          lo[2 * k + 1] = t[k];
+          hi[2 * k + 1] = hi[k];
+          lo[2 * k + 2] = lo[k];
+          hi[2 * k + 2] = t[k];
+        }
+      }
+      run_enclosed(d, st, s, nt, t, false, e);
+      ++np;
+      *n_kept = e.kept;
+      // walk the decisions of those iterations
+      bool done = false;
+      for (int k = 0, lvl = 0; lvl < lv; ++lvl, ++i) {
+        if ((right - left) < 0) {
+          *h_radius = (right + left) / 2;
+          *iterations = i;
+          done = true;
+          break;
+        }
+        const double mid = t[k];
+        const double z = target_rho - e.msum[k] / (4 * pi * std::pow(mid, 3.0) / 3);
+        if (std::fabs(z) < eta) {
+          *h_radius = mid;
+          *iterations = i + 1;
+          done = true;
+          break;
+        } else if (z < 0) {
+          left = mid;
+          k = 2 * k + 1;
+        } else {
+          right = mid;
+          k = 2 * k + 2;
+        }
+      }
+      if (done) {
+        *status = PBX_VIRIAL_CONVERGED;
+        break;
+      }
+    }
+    *passes = np;
   });
 }
 

@@ -183,6 +183,14 @@ _SIGNATURES: dict[str, tuple] = {
                                             POINTER(c_int), POINTER(c_int), _dp, _i64p, _dp]),
     "pbx_property_shrink_center": (c_int, [c_void_p, c_void_p, c_int64, c_int, _i64p, c_int,
                                            c_double, c_double, c_int64, _dp, _i64p, _i64p]),
+    "pbx_property_enclosed": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, _dp, _i64p, c_int,
+                                      c_int, _dp, c_int, POINTER(c_int), POINTER(c_int), _dp,
+                                      c_int, _dp, _i64p, _dp, _i64p, _dp]),
+    "pbx_property_virial_radius": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, _dp, _i64p,
+                                           c_int, c_int, _dp, c_int, POINTER(c_int),
+                                           POINTER(c_int), _dp, c_double, c_double, c_int, c_int,
+                                           c_double, c_int, _dp, _i64p, _i64p, _i64p,
+                                           POINTER(c_int)]),
     "pbx_comm_unique_id_size": (c_int, []),
     "pbx_comm_unique_id": (c_int, [c_char_p, c_int]),
     "pbx_comm_init": (c_int, [POINTER(c_void_p), c_int, c_int, c_char_p]),

@@ -142,7 +142,8 @@ class Frame:
             sl = sim._get_family_slice(f)
             if isinstance(sl, slice):  # (a view in no increasing order has no ranges)
                 families[f.name] = slice(*sl.indices(len(sim))[:2])
-        return SimSnap(arrays, families=families, units_map=units_map)
+        return SimSnap(arrays, families=families, units_map=units_map,
+                       properties=getattr(sim, "properties", None))
 
     def __repr__(self):
         parts = [f"{n}={getattr(self, n).tolist()}" for n in ("c", "vc", "R")
@@ -197,6 +198,10 @@ class FrameView(SimSnap):
 
     def keys(self):
         return self._frame_base.keys()
+
+    @property
+    def properties(self) -> dict:
+        return self._frame_base.properties
 
     def _array(self, key: str) -> np.ndarray:
         if key in ("pos", "vel"):

@@ -9,7 +9,16 @@ from .base import (
     SurfaceDensity,
     VolumeDensity,
 )
-from .generic import AngMomVec, CenPos, CenVel, KappaRot, KappaRotMean, PatternSpeed
+from .generic import (
+    AngMomVec,
+    CenPos,
+    CenVel,
+    KappaRot,
+    KappaRotMean,
+    PatternSpeed,
+    SpinParam,
+    VirialRadius,
+)
 
 __all__ = [
     "PropertyBase",
@@ -25,4 +34,6 @@ __all__ = [
     "CenVel",
     "AngMomVec",
     "PatternSpeed",
+    "VirialRadius",
+    "SpinParam",
 ]

@@ -1,7 +1,8 @@
 """Device route of the property calculators (libpbx, csrc/property.hip).
 
-Thin ctypes wrappers of pbx_property_moments(_frame, _region) and
-pbx_property_shrink_center (include/pbx.h, "scalar properties"), and the
+Thin ctypes wrappers of pbx_property_moments(_frame, _region),
+pbx_property_shrink_center, pbx_property_enclosed and
+pbx_property_virial_radius (include/pbx.h, "scalar properties"), and the
 conditions under which a property takes them: the source is a root
 ``SimSnap`` of the snapshot layer — or a FrameView of one, whose frame then
 rides along in the pass — whose ``pos`` / ``vel`` / ``mass`` are float64 and
@@ -26,6 +27,11 @@ ALL_GROUPS = 127
 NSUMS = 18
 POS_GROUPS = COM | ANGMOM | KAPPA | KAPPA_MEAN | PATTERN
 VEL_GROUPS = COV | ANGMOM | KAPPA | KAPPA_MEAN | PATTERN
+# the enclosed pass (pbx.h PBX_ENCLOSED_* / PBX_VIRIAL_LEVELS)
+ENCLOSED_MAX = 31
+ENCLOSED_NEXT = 7
+ENCLOSED_LEVELS = 5
+VIRIAL_LEVELS = 4
 
 _i64p = ctypes.POINTER(c_int64)
 
@@ -126,6 +132,61 @@ def shrink_center(pos, mass, *, r0: float, shrink_factor: float = 0.7, min_parti
              nat.dptr(cen), byref(it), byref(last))
     del keep
     return cen, it.value, last.value
+
+
+def _enclosed_scope(pos, mass, on_device, n, sphere, families, frame, region):
+    """The arguments pbx_property_enclosed and pbx_property_virial_radius
+    share, in order, and what has to outlive the call."""
+    ptrs, count, keep = _particle_args((pos, mass), on_device, n)
+    use_sphere, sph, fam, nfam = _scope_args(sphere, families)
+    framed = frame is not None and not frame.empty
+    fpacked = frame.packed() if framed else None
+    nc, kinds, neg, params = rg.packed(region)
+    args = (ptrs[0], ptrs[1], count, int(on_device), use_sphere, nat.dptr(sph),
+            fam.ctypes.data_as(_i64p), nfam, frame.flags if framed else 0, nat.dptr(fpacked), nc,
+            kinds, neg, nat.dptr(params))
+    return args, (keep, sph, fam, fpacked, kinds, neg, params)
+
+
+def enclosed(pos, mass, thresholds=(), *, sphere=None, families=None, on_device: bool = False,
+             n: int | None = None, frame=None, region=None,
+             extrema: bool = True) -> tuple[int, np.ndarray, np.ndarray, np.ndarray | None]:
+    """(n_kept, msum[nt], count[nt], ext[7] or None) of one enclosed pass
+    (pbx_property_enclosed): per threshold t the mass and the number of the
+    kept particles with ``sqrt((x*x + y*y) + z*z) < t`` (strict), and, with
+    ``extrema``, min x, max x, min y, max y, min z, max z, max r of the kept
+    particles (NaN when nothing is kept).  At most ENCLOSED_MAX thresholds;
+    none: the extrema and the count alone.  Scope arguments as in
+    :func:`moments`; mass None: unit masses."""
+    t = np.ascontiguousarray(np.asarray(thresholds, dtype=np.float64).reshape(-1))
+    args, alive = _enclosed_scope(pos, mass, on_device, n, sphere, families, frame, region)
+    kept = c_int64(0)
+    msum = np.zeros(max(t.size, 1))
+    count = np.zeros(max(t.size, 1), dtype=np.int64)
+    ext = np.zeros(ENCLOSED_NEXT) if extrema else None
+    nat.call("pbx_property_enclosed", *args, int(t.size), nat.dptr(t) if t.size else None,
+             byref(kept), nat.dptr(msum), count.ctypes.data_as(_i64p), nat.dptr(ext))
+    del alive
+    return kept.value, msum[:t.size], count[:t.size], ext
+
+
+def virial_radius(pos, mass, *, target_rho: float, eta: float, niter_max: int = 200,
+                  r_max: float | None = None, levels: int = 0, sphere=None, families=None,
+                  on_device: bool = False, n: int | None = None, frame=None,
+                  region=None) -> tuple[float, int, int, int, bool]:
+    """(radius, iterations, passes, n_kept, converged): the bisection of
+    simcore.virial_radius driven by the library over data that stays on the
+    device (pbx_property_virial_radius), ``levels`` bisection levels decided
+    per pass (0: the library's choice, VIRIAL_LEVELS).  r_max None:
+    max x - min x of the kept particles."""
+    args, alive = _enclosed_scope(pos, mass, on_device, n, sphere, families, frame, region)
+    radius = np.zeros(1)
+    it, passes, kept, status = c_int64(0), c_int64(0), c_int64(0), ctypes.c_int(0)
+    nat.call("pbx_property_virial_radius", *args, float(target_rho), float(eta), int(niter_max),
+             int(r_max is not None), 0.0 if r_max is None else float(r_max), int(levels),
+             nat.dptr(radius), byref(it), byref(passes), byref(kept), byref(status))
+    del alive
+    return float(radius[0]), it.value, passes.value, kept.value, status.value == 0
 
 
 # -- routing -------------------------------------------------------------------

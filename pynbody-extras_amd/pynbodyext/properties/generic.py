@@ -1,8 +1,10 @@
 """Generic property calculators — reference pynbodyext/properties/generic.py.
 
-Centres, bulk velocity, angular momentum, kappa_rot and the bar pattern
-speed, with the reference's numpy ``calculate`` on the host.  VirialRadius,
-SpinParam and CenPos("pot" / "hyb") are not provided.
+Centres, bulk velocity, angular momentum, kappa_rot, the virial radius, the
+spin parameter and the bar pattern speed, with the reference's numpy
+``calculate`` on the host.  VirialRadius and SpinParam call pynbody's
+``virial_radius`` / ``spin_parameter`` when pynbody is installed and their
+restatements in simcore otherwise.  CenPos("pot" / "hyb") is not provided.
 
 Device route (MI355X): each property names the sum groups it needs
 (``device_groups``, include/pbx.h PBX_PROP_*) and applies the reference's
@@ -12,6 +14,10 @@ family predicate applied in the same pass (csrc/property.hip).
 CenPos("ssc") runs the shrinking-sphere loop over data that stays on the
 device when the scope has no Sphere or region of its own.  The value's ``.sim`` is the
 root snapshot there (the masked sub-snapshot is never built).
+VirialRadius computes its target density on the host and hands the bisection
+to the library, which decides several levels per pass of the enclosed-mass
+kernel (pbx_property_virial_radius); SpinParam takes M and L from the
+MASS | ANGMOM pass and R from that kernel's extrema.
 """
 from __future__ import annotations
 
@@ -19,12 +25,13 @@ from typing import Any
 
 import numpy as np
 
-from .._pyn import HAVE_PYNBODY, SimArray, shrink_sphere_center
+from .._pyn import HAVE_PYNBODY, SimArray, shrink_sphere_center, spin_parameter, virial_radius
 from ..calculate import PropertyBase
-from ..simcore import shrink_sphere_r0
+from ..simcore import shrink_sphere_r0, spin_from_sums, virial_target_density
 from . import _device as dev
 
-__all__ = ["CenPos", "CenVel", "AngMomVec", "KappaRot", "KappaRotMean", "PatternSpeed"]
+__all__ = ["CenPos", "CenVel", "AngMomVec", "KappaRot", "KappaRotMean", "VirialRadius",
+           "SpinParam", "PatternSpeed"]
 
 
 class _MomentProperty(PropertyBase):
@@ -179,6 +186,85 @@ class KappaRotMean(_MomentProperty):
 
     def finish(self, n_kept, sums, sim) -> float:
         return float(_ratio(sums[12], n_kept))
+
+
+def _raise_empty():
+    """numpy's error for the max of nothing: what the host routes raise when
+    the scope keeps no particle (``sim["x"].max()``, ``sim["r"].max()``)."""
+    np.empty(0).max()
+
+
+@PropertyBase.dataclass
+class VirialRadius(PropertyBase):
+    """Virial radius property: the radius inside which the mean density is
+    ``overdensity`` times the critical ("critical") or the mean matter
+    ("matter") density at the snapshot's redshift.  The snapshot is taken as
+    centred on the origin; it reads ``sim.properties`` (h, omegaM0, omegaL0,
+    z)."""
+
+    overdensity: float = 178.
+    rho_def: str = "critical"
+
+    NITER_MAX = 200  # pynbody.util.bisect's default
+
+    def __post_init__(self) -> None:
+        if self.rho_def not in ("critical", "matter"):
+            raise ValueError(f"Invalid rho_def: {self.rho_def}. Expected one of ['critical', 'matter'].")
+
+    def calculate(self, sim, params: Any = None) -> float:
+        return virial_radius(sim, overden=params.overdensity, rho_def=params.rho_def)
+
+    def device_plan(self, source, spec, params):
+        base, frame = dev.unframe(source)  # (a FrameView: the pass reads its base in its frame)
+        arrs = dev.snapshot_arrays(base, ("pos", "mass"))
+        if arrs is None:
+            return None
+        target_rho = virial_target_density(source, params.overdensity, params.rho_def)
+        if not (np.isfinite(target_rho) and target_rho > 0):
+            return None
+
+        def run():
+            radius, _, _, n_kept, converged = dev.virial_radius(
+                arrs["pos"], arrs["mass"], target_rho=target_rho, eta=1.0e-3 * target_rho,
+                niter_max=self.NITER_MAX, sphere=spec.get("sphere"),
+                families=spec.get("families"), frame=frame, region=spec.get("region"))
+            if n_kept == 0:
+                _raise_empty()
+            if not converged:
+                raise ValueError("Bisection algorithm did not converge")
+            return radius
+
+        return run
+
+
+@PropertyBase.dataclass
+class SpinParam(PropertyBase):
+    """The spin parameter lambda' of eq. (5) of Bullock et al. 2001, MNRAS,
+    321, 559: J / (sqrt(2) M V R) with V = sqrt(G M / R).  The halo is taken
+    as centred on the origin with zero bulk velocity."""
+
+    def calculate(self, sim, params: Any = None) -> float:
+        return spin_parameter(sim)
+
+    def device_plan(self, source, spec, params):
+        base, frame = dev.unframe(source)
+        arrs = dev.snapshot_arrays(base, ("pos", "vel", "mass"))
+        if arrs is None:
+            return None
+        scope = dict(sphere=spec.get("sphere"), families=spec.get("families"), frame=frame,
+                     region=spec.get("region"))
+
+        def run():
+            # M and L from the MASS | ANGMOM pass, R from the extrema of the
+            # enclosed pass (no thresholds)
+            n_kept, sums = dev.moments(arrs["pos"], arrs["vel"], arrs["mass"],
+                                       groups=dev.MASS | dev.ANGMOM, **scope)
+            if n_kept == 0:
+                _raise_empty()
+            _, _, _, ext = dev.enclosed(arrs["pos"], arrs["mass"], **scope)
+            return spin_from_sums(sums[0], sums[7:10], ext[6], source)
+
+        return run
 
 
 @PropertyBase.dataclass

@@ -19,6 +19,9 @@ path needs a stand-in for the few pieces of pynbody its callers touch:
   expression and bits as ``vphi``) and ``ke = 0.5 * v2``,
   ``SimSnap.mean_by_mass`` and ``shrink_sphere_center`` (the stand-in for
   pynbody.analysis.halo's, whose algorithm is restated there);
+* what the halo calculators read: ``SimSnap.properties`` and ``rho_crit``,
+  ``virial_radius``, ``spin_parameter`` (stand-ins for
+  pynbody.analysis.cosmology / halo / angmom, restated there);
 * ``calc_faceon_matrix`` (pynbody.analysis.angmom's construction, restated
   there) for the transforms.
 
@@ -166,6 +169,7 @@ class _UnitsNamespace:
     UnitsException = UnitsException
     G = _UnitCls(*_SI["G"])
     kpc = _UnitCls(*_SI["kpc"])
+    Mpc = _UnitCls(*_SI["Mpc"])
     km = _UnitCls(*_SI["km"])
     s = _UnitCls(*_SI["s"])
     Msol = _UnitCls(*_SI["Msol"])
@@ -286,7 +290,11 @@ def kinematic_field(key: str, pos, vel) -> np.ndarray:
 class SimSnap:
     """A particle snapshot: named per-particle arrays + contiguous families."""
 
-    def __init__(self, arrays: dict, families: dict | None = None, units_map: dict | None = None):
+    def __init__(self, arrays: dict, families: dict | None = None, units_map: dict | None = None,
+                 properties: dict | None = None):
+        # pynbody's SimSnap.properties: the snapshot's scalars ("h", "omegaM0",
+        # "omegaL0", "z", ...); a plain dict, a missing key is a KeyError
+        self._properties: dict = dict(properties or {})
         self._arrays: dict[str, np.ndarray] = {}
         n = None
         for k, v in arrays.items():
@@ -426,6 +434,12 @@ class SimSnap:
     def ancestor(self) -> "SimSnap":
         return self
 
+    @property
+    def properties(self) -> dict:
+        """The root snapshot's dict (a sub-snapshot shows its ancestor's)."""
+        root = self.ancestor
+        return root._properties if root is self else root.properties
+
     def __repr__(self):
         return f"<SimSnap n={self._n} families={[f.name for f in self.families()]}>"
 
@@ -539,11 +553,127 @@ def is_pending(sim, key) -> bool:
 
 
 def new_snapshot(pos, mass, families: dict | None = None, units_map: dict | None = None,
-                 **arrays) -> SimSnap:
+                 properties: dict | None = None, **arrays) -> SimSnap:
     """Build a snapshot from (N,3) positions, (N,) masses and extra arrays."""
     arrs = {"pos": np.asarray(pos, dtype=np.float64), "mass": np.asarray(mass, dtype=np.float64)}
     arrs.update(arrays)
-    return SimSnap(arrs, families=families, units_map=units_map)
+    return SimSnap(arrs, families=families, units_map=units_map, properties=properties)
+
+
+# --------------------------------------------------------------------------
+# halo properties (stand-ins for pynbody.analysis.{cosmology,halo,angmom})
+# --------------------------------------------------------------------------
+def rho_crit(sim, z=None) -> float:
+    """Critical density at redshift ``z`` (default ``sim.properties["z"]``)
+    in units of ``sim["mass"].units / sim["pos"].units**3`` (the stand-in for
+    pynbody.analysis.cosmology.rho_crit; this statement is its contract)::
+
+        a = 1 / (1 + z);  omegaK = 1 - omegaM0 - omegaL0
+        H = 100 h km/s/Mpc * sqrt(omegaM0 a**-3 + omegaK a**-2 + omegaL0)
+        rho_crit = 3 H**2 / (8 pi G)
+
+    with h, omegaM0, omegaL0 from ``sim.properties`` (a missing one is a
+    KeyError).  Comoving units are not interpreted."""
+    props = sim.properties
+    if z is None:
+        z = props["z"]
+    h, om, ol = float(props["h"]), float(props["omegaM0"]), float(props["omegaL0"])
+    a = 1.0 / (1.0 + float(z))
+    hz = 100.0 * h * float(np.sqrt(om * a ** -3 + (1.0 - om - ol) * a ** -2 + ol))
+    hubble = hz * (units.km / units.s / units.Mpc)
+    rho = (hubble * hubble) * (3.0 / (8.0 * np.pi)) / units.G
+    return float(rho.ratio(sim["mass"].units / sim["pos"].units ** 3))
+
+
+def virial_target_density(sim, overden=178.0, rho_def="critical") -> float:
+    """``overden`` times the reference density of pynbody's virial_radius:
+    rho_crit(z) for "critical", omegaM0 * rho_crit(0) * (1 + z)**3 for
+    "matter"."""
+    if rho_def == "matter":
+        ref_density = (sim.properties["omegaM0"] * rho_crit(sim, z=0)
+                       * (1.0 + sim.properties["z"]) ** 3)
+    elif rho_def == "critical":
+        ref_density = rho_crit(sim, z=sim.properties["z"])
+    else:
+        raise ValueError(rho_def + " is not a valid definition for the reference density")
+    return float(overden * ref_density)
+
+
+def bisect_iterations(left, right, f, eta, niter_max=200):
+    """(root, iterations) of pynbody.util.bisect with epsilon = 0: the
+    midpoint at which ``abs(f(mid)) < eta``, and the number of midpoints
+    evaluated.  Not converged within ``niter_max``: ValueError."""
+    left, right = float(left), float(right)
+    for i in range(niter_max):
+        if (right - left) < 0:
+            return (right + left) / 2, i
+        mid = (left + right) / 2
+        z = f(mid)
+        if abs(z) < eta:
+            return mid, i + 1
+        elif z < 0:
+            left = mid
+        else:
+            right = mid
+    raise ValueError("Bisection algorithm did not converge")
+
+
+def virial_radius_iterations(sim, overden=178.0, rho_def="critical"):
+    """(radius, iterations) of :func:`virial_radius`."""
+    x = np.asarray(sim["x"])
+    r_max = float(x.max() - x.min())
+    target_rho = virial_target_density(sim, overden, rho_def)
+    mass_ar = np.asarray(sim["mass"])
+    r_ar = np.asarray(sim["r"])
+
+    def excess(r):  # (python floats: ** is libm's pow; NaN or 0 / 0 never passes a test)
+        with np.errstate(all="ignore"):
+            m_in = np.float64(np.dot(mass_ar, r_ar < r))
+            return float(target_rho - m_in / (4 * np.pi * r ** 3.0 / 3))
+
+    return bisect_iterations(0.0, r_max, excess, 1.0e-3 * target_rho)
+
+
+def virial_radius(sim, overden=178.0, rho_def="critical") -> float:
+    """The radius inside which the mean density is ``overden`` times the
+    reference density (the stand-in for pynbody.analysis.halo.virial_radius
+    without ``cen`` and ``r_max``; this statement is its contract, DESIGN.md
+    §6)::
+
+        r_max = x.max() - x.min();  target = overden * reference density
+        bisect on [0, r_max], at most 200 steps, for
+            target - dot(mass, r_arr < r) / (4 * pi * r**3 / 3)
+        until its magnitude is below 1e-3 * target
+
+    The snapshot is taken as centred on the origin."""
+    return virial_radius_iterations(sim, overden, rho_def)[0]
+
+
+def spin_parameter(sim) -> float:
+    """Bullock et al. 2001 (eq. 5) spin parameter of a centred halo at rest
+    (the stand-in for pynbody.analysis.angmom.spin_parameter; this statement
+    is its contract)::
+
+        M = mass.sum();  R = r.max();  V = sqrt(G M / R) in vel units
+        J = |sum m (pos x vel)|;  lambda' = J / (sqrt(2) M V R)"""
+    mass = np.asarray(sim["mass"])
+    m_tot = mass.sum()
+    r_max = np.asarray(sim["r"]).max()
+    ang = (mass.reshape((len(mass), 1)) * np.cross(np.asarray(sim["pos"]),
+                                                  np.asarray(sim["vel"]))).sum(axis=0)
+    return spin_from_sums(m_tot, ang, r_max, sim)
+
+
+def spin_from_sums(m_tot, ang, r_max, sim) -> float:
+    """lambda' from M, the angular momentum vector and R (spin_parameter's
+    final arithmetic, shared with the device route)."""
+    m_tot, r_max = float(m_tot), float(r_max)
+    g = float((units.G * sim._unit_of("mass") / sim._unit_of("pos")).ratio(sim._unit_of("vel") ** 2))
+    ang = np.asarray(ang, dtype=np.float64)
+    with np.errstate(all="ignore"):
+        v = np.sqrt(np.float64(g) * m_tot / r_max)
+        j = np.sqrt((ang * ang).sum())
+        return float(j / (np.sqrt(2.0) * m_tot * v * r_max))
 
 
 def shrink_sphere_center(sim, r=None, shrink_factor=0.7, min_particles=100, **kwargs) -> SimArray:
