@@ -35,7 +35,9 @@
  * restatement is pinned by the reference's own property tests re-run on it
  * (crates/gravity/tests/gravity_tests.rs, single_node.rs,
  * translate_multipole.rs — tests/test_oracle_tree.py) plus known-answer
- * tests; absolute parity with the Rust binary is "unpinned" beyond those.
+ * tests, and every order of the moments, the evaluators and the walk by a
+ * long-double Legendre series (tests/test_oracle_multipole.py); the Rust
+ * binary's own bits stay "unpinned".
  */
 #include <math.h>
 #include <stdint.h>
