@@ -408,13 +408,28 @@ int pbx_profile_kinematic_field(void *handle, int code, double *h_out);
 int pbx_profile_kinematic_moments(void *handle, int n_fields, const int *codes, int w_src,
                                   const double *h_w, const uint32_t *cols, double *h_out);
 /* The frame a handle reads particles in: an optional position shift c, an
- * optional velocity shift vc and an optional rotation R (row-major 3 x 3),
- * packed as frame[15] = {c[3], vc[3], R[9]} with one PBX_FRAME_* flag per
- * step.  Per particle, in float64 without FMA contraction, in this order:
+ * optional velocity shift vc, an optional periodic wrap of the positions
+ * (box size L, lower bound lo per axis) and an optional rotation R
+ * (row-major 3 x 3), packed as frame[15] = {c[3], vc[3], R[9]}, or as
+ * frame[19] = {c[3], vc[3], R[9], L, lo[3]} with PBX_FRAME_WRAP, with one
+ * PBX_FRAME_* flag per step.  Per particle, in float64 without FMA
+ * contraction, in this order:
  *   dx = x - c0;  dy = y - c1;  dz = z - c2            (PBX_FRAME_POS)
+ *   k  = floor((dx - lo0) / L) + 0.0;  dx = dx - k*L;  the same for dy, dz
+ *                                                      (PBX_FRAME_WRAP)
  *   x' = (R00*dx + R01*dy) + R02*dz;  y' = (R10*dx + R11*dy) + R12*dz;
  *   z' = (R20*dx + R21*dy) + R22*dz                    (PBX_FRAME_ROT)
- * and the same for v with vc (PBX_FRAME_VEL, PBX_FRAME_ROT).  A step whose
+ * and the same for v with vc (PBX_FRAME_VEL, PBX_FRAME_ROT; a velocity is
+ * never wrapped).  The wrap restates WrapBox of the reference
+ * (transforms/wrap.py:117-213) into [lo, lo + L): lo[k] is -0.5*L (its
+ * "center") or 0.0 ("upper"), "/" is IEEE division (no reciprocal), and the
+ * "+ 0.0" turns a -0.0 from floor into +0.0, as the reference's integer k
+ * does, so that -0.0 stays -0.0.  A non-finite coordinate follows the
+ * statement (inf - inf*L is NaN).  frame[15..18] is read ONLY when
+ * PBX_FRAME_WRAP is set: without it a frame is 15 numbers, as before.
+ * PBX_FRAME_WRAP with L not finite or L <= 0, or with a lo[k] other than
+ * -0.5*L or 0.0, is a PBX_ERR_VALUE whose message names PBX_FRAME_WRAP.  Bit
+ * 8 is unassigned and, like every other unknown bit, an error.  A step whose
  * flag is off is skipped, not run with zeros or the identity (0 * inf would
  * turn an infinite coordinate into NaN).  Everything downstream is computed
  * from x', v' exactly as it is from x, v without a frame: the Sphere test of
@@ -438,6 +453,7 @@ int pbx_profile_kinematic_moments(void *handle, int n_fields, const int *codes, 
 #define PBX_FRAME_POS 1
 #define PBX_FRAME_VEL 2
 #define PBX_FRAME_ROT 4
+#define PBX_FRAME_WRAP 16
 int pbx_profile_set_frame(void *handle, int flags, const double *frame);
 /* The region a handle keeps particles in: a conjunction of nclauses <=
  * PBX_REGION_MAX clauses, each one primitive (kinds[c]), negated when
@@ -666,7 +682,8 @@ int pbx_property_moments(const double *pos, const double *vel, const double *mas
                          int on_device, int use_sphere, const double *sphere,
                          const int64_t *fam, int nfam, uint32_t groups, int64_t *n_kept,
                          double *h_sums);
-/* The same pass in a frame (flags / frame[15] as in pbx_profile_set_frame;
+/* The same pass in a frame (flags / frame as in pbx_profile_set_frame: 15
+ * numbers, and frame[15..18] read only when PBX_FRAME_WRAP is set;
  * flags == 0 or frame == NULL: exactly pbx_property_moments).  Positions and
  * velocities are taken to the frame first; the Sphere test (its centre in
  * frame coordinates) and every term are then evaluated from x', v' as above.
@@ -682,7 +699,8 @@ int pbx_property_moments_frame(const double *pos, const double *vel, const doubl
                                const double *frame, int64_t *n_kept, double *h_sums);
 /* The same pass in a frame and a region (nclauses / kinds / negate / params
  * as in pbx_profile_set_region; nclauses == 0: exactly
- * pbx_property_moments_frame).  A particle is kept when the families, the
+ * pbx_property_moments_frame; frame[15..18] is read only when
+ * PBX_FRAME_WRAP is set).  A particle is kept when the families, the
  * Sphere (if any) and every clause of the region hold, the clauses evaluated
  * on the frame's coordinates.  pos is read whenever a region is present.  The
  * region is a template parameter of the kernel beside the frame: the
@@ -716,7 +734,8 @@ int pbx_property_shrink_center(const double *pos, const double *mass, int64_t n,
  * start from (x.max() - x.min(), r.max()).  Stateless; pos / mass, on_device,
  * the sphere, the families, flags / frame and the region clauses as in
  * pbx_property_moments_region, with the same meaning: a particle is kept as
- * that pass keeps it, and x, y, z below are the frame's coordinates.  Per
+ * that pass keeps it, and x, y, z below are the frame's coordinates
+ * (frame[15..18] is read only when PBX_FRAME_WRAP is set).  Per
  * kept particle, without FMA contraction, with a correctly rounded sqrt and
  * m = mass (1.0 when mass is NULL):
  *   r = sqrt((x*x + y*y) + z*z)
@@ -755,7 +774,8 @@ int pbx_property_enclosed(const double *pos, const double *mass, int64_t n, int 
 /* The virial radius of the kept particles: the radius at which the mean
  * enclosed density M(<r) / (4 pi r^3 / 3) equals target_rho, by the bisection
  * of pynbody's analysis.halo.virial_radius (util.bisect with epsilon = 0).
- * The scope arguments are those of the enclosed pass.  The particles are
+ * The scope arguments are those of the enclosed pass (frame[15..18] is read
+ * only when PBX_FRAME_WRAP is set).  The particles are
  * staged once (or borrowed, on_device = 1) and the enclosed pass runs over
  * them, one read-back per pass.  Without has_rmax, r_max = max x - min x of
  * the kept particles, from one extrema pass (nt = 0).  The loop, in host
@@ -795,6 +815,27 @@ int pbx_property_virial_radius(const double *pos, const double *mass, int64_t n,
                                double eta, int niter_max, int has_rmax, double r_max, int levels,
                                double *h_radius, int64_t *iterations, int64_t *passes,
                                int64_t *n_kept, int *status);
+
+/* The extents WrapBox("minirange") chooses its convention from
+ * (transforms/wrap.py:161-211 of the reference: both candidate wraps of every
+ * axis, their max() - min(), the smaller range wins): one streaming pass over
+ * pos[0:n] (n x 3 doubles, host or device), every particle, no predicate.
+ * flags / frame as in pbx_profile_set_frame, restricted to what can precede a
+ * wrap: PBX_FRAME_POS (the shift is applied first) and PBX_FRAME_VEL (ignored:
+ * velocities are not read); PBX_FRAME_ROT or PBX_FRAME_WRAP is a
+ * PBX_ERR_VALUE, and so is L not finite or L <= 0.  Per axis a, with the wrap
+ * step of the frame for lo = -0.5*L (wc) and lo = 0.0 (wu):
+ *   h_ext[4*a + 0] = min wc,  h_ext[4*a + 1] = max wc,
+ *   h_ext[4*a + 2] = min wu,  h_ext[4*a + 3] = max wu
+ * with numpy's rule for min / max: a NaN among an axis's values makes its
+ * four numbers NaN (and the other axes' none).  The values are numpy's bit
+ * for bit, except the sign of an extremum that is a zero when both zeros
+ * occur (numpy's own choice there depends on its reduction order); a range
+ * max - min does not depend on it.  n == 0: the identities, +inf for a min
+ * and -inf for a max, PBX_OK.  No atomics; a min / max does not depend on the
+ * order of the fold.  The axis choice is the caller's. */
+int pbx_property_wrap_extents(const double *pos, int64_t n, int on_device, int flags,
+                              const double *frame, double L, double *h_ext);
 
 /* ------------------------------------------------------------------ */
 /* multi-GPU: RCCL communicator (one process per GPU, over xGMI)       */

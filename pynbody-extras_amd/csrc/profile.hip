@@ -56,12 +56,23 @@ struct SelectParams {
   double cx, cy, cz, r2max;
   int64_t fam_lo[MAX_FAM];
   int64_t fam_hi[MAX_FAM];
-  FrameHalf fr;  // the handle's frame for positions (pbx_profile_set_frame); float64 only
+  // the handle's frame for positions (pbx_profile_set_frame), without its
+  // wrap; float64 only
+  FrameHalf fr;
   // the handle's region (pbx_profile_set_region), ANDed in by the kernels
   // instantiated for one (null: none); float64 only.  A pointer to the
   // handle's device copy, not the 400 bytes themselves: every kernel that
-  // takes a SelectParams would carry them in its arguments, region or not
+  // takes a SelectParams would carry them in its arguments, region or not.
+  // The copy is a SelectExtra: the frame's wrap sits behind the region, so a
+  // handle with a wrap runs the same instantiations (with a region of no
+  // clauses when none is set) and a SelectParams is what it was without one
   const Region *rg;
+};
+
+// the handle's device block behind SelectParams::rg
+struct SelectExtra {
+  Region rg;
+  FrameWrap wrap;
 };
 
 // family membership of particle i (contiguous slices; no slices = all)
@@ -79,8 +90,8 @@ __device__ __forceinline__ bool in_family(int64_t i, const SelectParams &p) {
 // is evaluated in double on the exactly widened coordinates; r / rxy of the
 // float32 array stay float32 arithmetic (its float32 values are stored
 // widened, exactly).
-// RG: the kernel honours the handle's region (*p.rg, region.h; p.rg is then
-// not null).  The selection kernels are instantiated with and without it and
+// RG: the kernel honours the handle's region and its frame's wrap (*p.rg, a
+// SelectExtra; region.h, frame.h; p.rg is then not null).  The selection kernels are instantiated with and without it and
 // launched by whether a region is set, so that a region-less selection runs
 // the region-less code.
 template <typename T, bool RG>
@@ -89,7 +100,12 @@ __device__ __forceinline__ bool select_xyz(T px, T py, T pz, const SelectParams 
   if constexpr (std::is_same<T, double>::value) {
     // the frame first (uniform: a scalar branch); everything below then reads
     // the frame's coordinates, the origin shortcut included
-    if (__builtin_expect(p.fr.shift | p.fr.rot, 0)) frame_apply(p.fr, px, py, pz);
+    if constexpr (RG) {
+      const FrameWrap &wr = reinterpret_cast<const SelectExtra *>(p.rg)->wrap;
+      if (__builtin_expect(p.fr.shift | wr.on | p.fr.rot, 0)) frame_apply(p.fr, wr, px, py, pz);
+    } else {
+      if (__builtin_expect(p.fr.shift | p.fr.rot, 0)) frame_apply(p.fr, px, py, pz);
+    }
     // a Sphere at the origin: dx = x - 0.0 is x exactly (NaN and -0.0
     // included), so ((dx*dx + dy*dy) + dz*dz) is r^2 itself — one sum of
     // squares for both the test and r
@@ -1702,7 +1718,9 @@ __device__ void xsrc_tiles(const XSrc &xs, uint32_t ta, uint32_t tb) {
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       double xv = 0.0;
-      // (a kept slot passed the region when its keep bit was set: not evaluated again)
+      // (a kept slot passed the region when its keep bit was set: not evaluated
+      // again.  A frame with a wrap never gets here: its calls do not speculate
+      // and keep their x: the speculation test of the tiled call)
       if (kp[u] && select_xyz<double, false>(px[u], py[u], pz[u], xs.sp, xv))
         xs.x[a + (int64_t)u * bt] = xv;
     }
@@ -4523,17 +4541,18 @@ __device__ __forceinline__ double kin_pick(const double f[KIN_NF], int code) {
 }
 
 // one field in selection order (idx NULL: identity, a set_x handle)
+template <bool WRAP>
 __global__ void __launch_bounds__(TPB)
     kin_field_kernel(const int32_t *__restrict__ idx, const double *__restrict__ pos,
-                     const double *__restrict__ vel, int64_t n, int code, Frame fr, int framed,
-                     double *__restrict__ out) {
+                     const double *__restrict__ vel, int64_t n, int code, FrameK<WRAP> fr,
+                     int framed, double *__restrict__ out) {
   const int64_t t = (int64_t)blockIdx.x * TPB + threadIdx.x;
   if (t >= n) return;
   const int64_t i = idx ? (int64_t)idx[t] : t;
   double p[3] = {pos[3 * i], pos[3 * i + 1], pos[3 * i + 2]};
   double v[3] = {vel[3 * i], vel[3 * i + 1], vel[3 * i + 2]};
   if (framed) {
-    frame_apply(fr.pos, p[0], p[1], p[2]);
+    frame_apply_pos(fr, p[0], p[1], p[2]);
     frame_apply(fr.vel, v[0], v[1], v[2]);
   }
   double f[KIN_NF];
@@ -4553,11 +4572,12 @@ struct KinPlan {
   int8_t slot[KIN_NF][NMOM];   // columns 1..6 of field k (-1: not accumulated)
 };
 
+template <bool WRAP>
 __global__ void __launch_bounds__(TPB)
     kin_moments_kernel(const uint32_t *__restrict__ bins, const int32_t *__restrict__ idx,
                        const double *__restrict__ wt, const double *__restrict__ pos,
-                       const double *__restrict__ vel, int64_t n, int nb, KinPlan plan, Frame fr,
-                       int framed, int copies, double *__restrict__ slab) {
+                       const double *__restrict__ vel, int64_t n, int nb, KinPlan plan,
+                       FrameK<WRAP> fr, int framed, int copies, double *__restrict__ slab) {
   extern __shared__ double acc_lds[];
   const int len = nb * plan.nslots;
   // (copies: as in moments_kernel — a copy per wave, or one copy and turns)
@@ -4589,7 +4609,7 @@ __global__ void __launch_bounds__(TPB)
     for (int k = 0; k < KIN_IPT; ++k) {
       if (bv[k] >= (uint32_t)nb) continue;
       if (framed) {  // (uniform)
-        frame_apply(fr.pos, p[k][0], p[k][1], p[k][2]);
+        frame_apply_pos(fr, p[k][0], p[k][1], p[k][2]);
         frame_apply(fr.vel, v[k][0], v[k][1], v[k][2]);
       }
       kin_fields(p[k], v[k], plan.need, fk[k]);
@@ -5087,7 +5107,7 @@ struct Profile {
   Frame frame{};
   // pbx_profile_set_region: the region every selection ANDs in (sticky; n == 0 = none)
   Region region{};
-  Buf rgdev;  // its device copy (what SelectParams points to)
+  Buf rgdev;  // the device copy of region and frame.wrap (a SelectExtra: what SelectParams points to)
   bool posst_sel = false;  // posst holds this selection's positions (a lazy selection of host arrays)
 };
 
@@ -5448,7 +5468,7 @@ static SelPrep select_prep(Profile &P, hipStream_t st, const SelectReq &q, bool 
   sp.fr = P.frame.pos;
   if (pos_f32 && P.region.any())
     fail(PBX_ERR_VALUE, "a region is set on this handle: float32 positions are not supported");
-  sp.rg = P.region.any() ? (const Region *)P.rgdev.p : nullptr;
+  sp.rg = (P.region.any() || P.frame.wrap.on) ? (const Region *)P.rgdev.p : nullptr;
   sp.mass_f32 = mass_f32;
   const size_t ps = pos_f32 ? sizeof(float) : sizeof(double);
   const size_t ms = mass_f32 ? sizeof(float) : sizeof(double);
@@ -5731,8 +5751,13 @@ static void kin_field_device(Profile &P, hipStream_t st, int code, double *out) 
   const int64_t n = P.n;
   if (!n) return;
   const int32_t *idx = kin_idx(P, st);
-  hipLaunchKernelGGL(kin_field_kernel, dim3(ceil_div(n, TPB)), dim3(TPB), 0, st, idx, P.kin_pos,
-                     P.kin_vel, n, code, P.frame, (int)P.frame.any(), out);
+  // (a frame with a wrap: the instantiation that carries its constants)
+  if (P.frame.wrap.on)
+    hipLaunchKernelGGL(kin_field_kernel<true>, dim3(ceil_div(n, TPB)), dim3(TPB), 0, st, idx,
+                       P.kin_pos, P.kin_vel, n, code, P.frame.k<true>(), 1, out);
+  else
+    hipLaunchKernelGGL(kin_field_kernel<false>, dim3(ceil_div(n, TPB)), dim3(TPB), 0, st, idx,
+                       P.kin_pos, P.kin_vel, n, code, P.frame.k<false>(), (int)P.frame.any(), out);
   PBX_HIP(hipGetLastError());
 }
 
@@ -6273,11 +6298,12 @@ inline void RadialCall::select(const SelectReq &q) {
   // bins with it (checked by fused_resolve; a miss takes assign_tiles).
   // It stores no x, which is then rebuilt from the positions on demand:
   // only from positions the handle owns (staged host arrays) or that the
-  // caller declared stable
+  // caller declared stable, and never in a frame with a wrap (the rebuild,
+  // xsrc_tiles, is the wrap-less code: such calls keep their x)
   bool spec_ops = true;  // select_tiles' sums take the dedicated monomials only
   for (int k = 0; k < fs.nm; ++k) spec_ops = spec_ops && fs.op[k] != MO_GEN;
   if (hints && P.spec_next && P.stab.p && nb <= SPEC_MAXB && fs.nm * nb <= SPEC_MACC && spec_ops &&
-      (!q.on_device || P.src_stable)) {
+      (!q.on_device || P.src_stable) && !P.frame.wrap.on) {
     thist.sa.tab = (const SpecTab *)P.stab.p;
     thist.sa.fs = fs;
     thist.sa.nb = (int)nb;
@@ -7166,15 +7192,26 @@ int pbx_profile_set_kinematics(void *handle, const double *pos, const double *ve
   });
 }
 
+// The handle's region and its frame's wrap to the device block the selection
+// kernels read (SelectExtra), when there is either.  Stream-ordered after the
+// kernels of earlier selections that read the old one; waited for, since the
+// source is a local.
+static void upload_select_extra(Profile &P, hipStream_t st) {
+  if (!P.region.any() && !P.frame.wrap.on) return;
+  const SelectExtra ex{P.region, P.frame.wrap};
+  PBX_HIP(hipMemcpyAsync(P.rgdev.get(sizeof(SelectExtra)), &ex, sizeof(SelectExtra),
+                         hipMemcpyHostToDevice, st));
+  PBX_HIP(hipStreamSynchronize(st));
+}
+
 // The frame the handle reads particles in (frame.h): honoured by the next
 // selections (select_prep -> select_xyz) and by the kinematic fields.  Sticky;
 // flags == 0 or a NULL frame clears it.
 int pbx_profile_set_frame(void *handle, int flags, const double *frame) {
   return with_profile(handle, [&](Profile &P, Device &d, hipStream_t st) {
-    if (flags & ~(PBX_FRAME_POS | PBX_FRAME_VEL | PBX_FRAME_ROT))
-      fail(PBX_ERR_VALUE, "flags must be a mask of PBX_FRAME_* bits (got 0x%x)", flags);
-    P.frame = frame_of(flags, frame);
+    P.frame = frame_of(flags, frame);  // (checks the flags and the wrap)
     P.cum_valid = false;
+    upload_select_extra(P, st);
   });
 }
 
@@ -7185,13 +7222,7 @@ int pbx_profile_set_region(void *handle, int nclauses, const int *kinds, const i
   return with_profile(handle, [&](Profile &P, Device &d, hipStream_t st) {
     P.region = region_of(nclauses, kinds, negate, params);
     P.cum_valid = false;
-    // (stream-ordered after the kernels of earlier selections that read the
-    // old one; waited for, since the source is the handle's own member)
-    if (P.region.any()) {
-      PBX_HIP(hipMemcpyAsync(P.rgdev.get(sizeof(Region)), &P.region, sizeof(Region),
-                             hipMemcpyHostToDevice, st));
-      PBX_HIP(hipStreamSynchronize(st));
-    }
+    upload_select_extra(P, st);
   });
 }
 
@@ -7261,10 +7292,16 @@ int pbx_profile_kinematic_moments(void *handle, int n_fields, const int *codes, 
     double *acc = (double *)P.acc.get(sizeof(double) * (size_t)plen);
     double *part = (double *)P.slabp.get(sizeof(double) * (size_t)SLAB_G * plen);
     const int copies = lds_copies(plen);
-    hipLaunchKernelGGL(kin_moments_kernel, dim3(nt), dim3(TPB),
-                       sizeof(double) * (size_t)plen * copies, st,
-                       (const uint32_t *)P.bins.p, idx, w, P.kin_pos, P.kin_vel, n, (int)nb, plan,
-                       P.frame, (int)P.frame.any(), copies, slab);
+    if (P.frame.wrap.on)
+      hipLaunchKernelGGL(kin_moments_kernel<true>, dim3(nt), dim3(TPB),
+                         sizeof(double) * (size_t)plen * copies, st, (const uint32_t *)P.bins.p, idx,
+                         w, P.kin_pos, P.kin_vel, n, (int)nb, plan, P.frame.k<true>(), 1, copies,
+                         slab);
+    else
+      hipLaunchKernelGGL(kin_moments_kernel<false>, dim3(nt), dim3(TPB),
+                         sizeof(double) * (size_t)plen * copies, st, (const uint32_t *)P.bins.p, idx,
+                         w, P.kin_pos, P.kin_vel, n, (int)nb, plan, P.frame.k<false>(),
+                         (int)P.frame.any(), copies, slab);
     PBX_HIP(hipGetLastError());
     hipLaunchKernelGGL(reduce_slab_part, dim3(ceil_div(plen, TPB), SLAB_G), dim3(TPB), 0, st, slab,
                        (int64_t)nt, plen, part);

@@ -81,12 +81,14 @@ __device__ __forceinline__ bool prop_in_sphere(double x, double y, double z, con
 // the sphere test and the terms (frame.h); without it fr is not looked at and
 // the pass is the frame-less one.  REGION (POS only): the clauses of rg are
 // ANDed into the predicate on the same coordinates (region.h); without it rg
-// is not looked at and the pass is the region-less one.  part: one row of NS
-// sums per block; cnt: its count.
-template <bool POS, bool VEL, bool FRAME, bool REGION = false>
+// is not looked at and the pass is the region-less one.  WRAP (FRAME and POS
+// only): the frame holds a periodic wrap; without it the kernel takes
+// FrameK<false>, the argument block it had before the wrap existed.  part: one
+// row of NS sums per block; cnt: its count.
+template <bool POS, bool VEL, bool FRAME, bool REGION = false, bool WRAP = false>
 __global__ void __launch_bounds__(PROP_TPB)
     property_moments(const double *__restrict__ pos, const double *__restrict__ vel,
-                     const double *__restrict__ mass, PropParams p, Frame fr, Region rg,
+                     const double *__restrict__ mass, PropParams p, FrameK<WRAP> fr, Region rg,
                      uint32_t groups, double *__restrict__ part, long long *__restrict__ cnt) {
 #pragma clang fp contract(off)
   __shared__ double ws[PROP_NW][NS];
@@ -124,7 +126,7 @@ __global__ void __launch_bounds__(PROP_TPB)
     if constexpr (FRAME) {
 #pragma unroll
       for (int k = 0; k < PROP_ITEMS; ++k) {
-        if constexpr (POS) frame_apply(fr.pos, x[k], y[k], z[k]);
+        if constexpr (POS) frame_apply_pos(fr, x[k], y[k], z[k]);
         if constexpr (VEL) frame_apply(fr.vel, vx[k], vy[k], vz[k]);
       }
     }
@@ -286,11 +288,13 @@ __device__ __forceinline__ double enc_identity(int col) {
 }
 
 // NTC: the thresholds the instantiation holds (nt rounded up to 2^L - 1).
-// FRAME / REGION as in property_moments.  want_ext (uniform): the extrema.
-template <int NTC, bool FRAME, bool REGION>
+// FRAME / REGION / WRAP as in property_moments.  want_ext (uniform): the
+// extrema.
+template <int NTC, bool FRAME, bool REGION, bool WRAP = false>
 __global__ void __launch_bounds__(PROP_TPB)
     property_enclosed(const double *__restrict__ pos, const double *__restrict__ mass, PropParams p,
-                      Frame fr, Region rg, EncThresholds<NTC> th, int want_ext, EncPart out) {
+                      FrameK<WRAP> fr, Region rg, EncThresholds<NTC> th, int want_ext,
+                      EncPart out) {
 #pragma clang fp contract(off)
   __shared__ double ws[PROP_NW][NTC];
   __shared__ long long wc[PROP_NW][NTC + 1];
@@ -324,7 +328,7 @@ __global__ void __launch_bounds__(PROP_TPB)
     }
     if constexpr (FRAME) {
 #pragma unroll
-      for (int k = 0; k < PROP_ITEMS; ++k) frame_apply(fr.pos, x[k], y[k], z[k]);
+      for (int k = 0; k < PROP_ITEMS; ++k) frame_apply_pos(fr, x[k], y[k], z[k]);
     }
     if (p.use_sphere) {
 #pragma unroll
@@ -491,6 +495,105 @@ __global__ void __launch_bounds__(PROP_RG *ENC_RCOLS)
   }
 }
 
+// ----------------------------------------------------------- wrap extents
+// pbx_property_wrap_extents: what WrapBox("minirange") asks of the particles
+// before it can choose a convention per axis.  One read of pos[0:n] (24 bytes
+// per particle), no predicate; per axis both candidate wraps of frame.h
+// (lo = -0.5 * L and lo = 0.0) and their min / max with numpy's NaN rule.
+// Column 4 * axis + {0 min wc, 1 max wc, 2 min wu, 3 max wu}.  The grid, the
+// particle -> thread mapping and the three fold steps are those of
+// property_enclosed's extrema; a min / max does not depend on the order, so
+// the result depends on the particles alone.
+constexpr int WEXT_N = 12;
+constexpr int WEXT_RCOLS = 16;  // columns of wrap_extents_reduce (>= WEXT_N)
+static_assert(WEXT_N <= WEXT_RCOLS && WEXT_N <= PROP_TPB, "wrap extents columns");
+
+__device__ __forceinline__ double wext_fold(int col, double a, double v) {
+  return (col & 1) ? enc_max(a, v) : enc_min(a, v);
+}
+__device__ __forceinline__ double wext_identity(int col) {
+  return (col & 1) ? -__builtin_inf() : __builtin_inf();
+}
+
+__global__ void __launch_bounds__(PROP_TPB)
+    property_wrap_extents(const double *__restrict__ pos, int64_t n, FrameHalf sh, double L,
+                          double lo_c, double *__restrict__ part) {  // (sh: its shift only)
+#pragma clang fp contract(off)
+  __shared__ double we[PROP_NW][WEXT_N];
+  double ex[WEXT_N];
+#pragma unroll
+  for (int e = 0; e < WEXT_N; ++e) ex[e] = wext_identity(e);
+  const int64_t stride = (int64_t)gridDim.x * PROP_TPB;
+  for (int64_t j0 = (int64_t)blockIdx.x * PROP_TPB + threadIdx.x; j0 < n;
+       j0 += stride * PROP_ITEMS) {
+    double v[PROP_ITEMS][3];
+    bool in[PROP_ITEMS];
+    // (as property_enclosed: every load of the sweep in flight, a slot past
+    // the end reads particle 0 and is folded into nothing)
+#pragma unroll
+    for (int k = 0; k < PROP_ITEMS; ++k) {
+      const int64_t j = j0 + k * stride;
+      in[k] = j < n;
+      const double *q = pos + 3 * (in[k] ? j : 0);
+      v[k][0] = q[0];
+      v[k][1] = q[1];
+      v[k][2] = q[2];
+    }
+#pragma unroll
+    for (int k = 0; k < PROP_ITEMS; ++k) {
+      if (sh.shift) {  // (uniform)
+        v[k][0] = v[k][0] - sh.c[0];
+        v[k][1] = v[k][1] - sh.c[1];
+        v[k][2] = v[k][2] - sh.c[2];
+      }
+#pragma unroll
+      for (int a = 0; a < 3; ++a) {
+        // the wrap step of frame_apply with either lower bound
+        const double x = v[k][a];
+        const double wc = x - (__builtin_floor((x - lo_c) / L) + 0.0) * L;
+        const double wu = x - (__builtin_floor((x - 0.0) / L) + 0.0) * L;
+        ex[4 * a + 0] = in[k] ? enc_min(ex[4 * a + 0], wc) : ex[4 * a + 0];
+        ex[4 * a + 1] = in[k] ? enc_max(ex[4 * a + 1], wc) : ex[4 * a + 1];
+        ex[4 * a + 2] = in[k] ? enc_min(ex[4 * a + 2], wu) : ex[4 * a + 2];
+        ex[4 * a + 3] = in[k] ? enc_max(ex[4 * a + 3], wu) : ex[4 * a + 3];
+      }
+    }
+  }
+#pragma unroll
+  for (int e = 0; e < WEXT_N; ++e) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) ex[e] = wext_fold(e, ex[e], __shfl_xor(ex[e], o, 64));
+  }
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  if (lane == 0) {
+#pragma unroll
+    for (int e = 0; e < WEXT_N; ++e) we[w][e] = ex[e];
+  }
+  __syncthreads();
+  const int t = threadIdx.x;
+  if (t < WEXT_N) {
+    double s = we[0][t];
+    for (int ww = 1; ww < PROP_NW; ++ww) s = wext_fold(t, s, we[ww][t]);
+    part[(int64_t)blockIdx.x * WEXT_N + t] = s;
+  }
+}
+
+// the rows of a wrap-extents pass in the order of enclosed_reduce; one block
+// of PROP_RG * WEXT_RCOLS threads, res: WEXT_N doubles
+__global__ void __launch_bounds__(PROP_RG *WEXT_RCOLS)
+    wrap_extents_reduce(const double *__restrict__ part, int rows, double *__restrict__ res) {
+  __shared__ double gd[PROP_RG][WEXT_RCOLS];
+  const int g = threadIdx.x / WEXT_RCOLS, col = threadIdx.x % WEXT_RCOLS;
+  const bool has = col < WEXT_N;
+  const auto fold = [col](double a, double b) { return wext_fold(col, a, b); };
+  if (has) gd[g][col] = enc_fold_rows(part + col, WEXT_N, g, rows, wext_identity(col), fold);
+  __syncthreads();
+  if (g != 0 || !has) return;
+  double s = wext_identity(col);
+  for (int k = 0; k < PROP_RG; ++k) s = wext_fold(col, s, gd[k][col]);
+  res[col] = s;
+}
+
 // ------------------------------------------------------------------- host
 // blocks of a pass over `span` particles (a function of span alone)
 static int grid_of(int64_t span) {
@@ -577,13 +680,22 @@ static void run_pass(Device &d, hipStream_t st, const Staged &s, uint32_t groups
   const bool use_pos = s.p.use_sphere || s.rg.any() || (groups & POS_GROUPS);
   const bool use_vel = (groups & VEL_GROUPS) != 0;
   auto launch = [&](auto kern) {
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(PROP_TPB), 0, st, s.pos, s.vel, s.mass, s.p, s.fr,
-                       s.rg, groups, part, cnt);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(PROP_TPB), 0, st, s.pos, s.vel, s.mass, s.p,
+                       s.fr.k<false>(), s.rg, groups, part, cnt);
+  };
+  auto launch_wrap = [&](auto kern) {
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(PROP_TPB), 0, st, s.pos, s.vel, s.mass, s.p,
+                       s.fr.k<true>(), s.rg, groups, part, cnt);
   };
   // (a frame half whose array the pass does not read changes nothing)
-  const bool framed = (use_pos && (s.fr.pos.shift || s.fr.pos.rot)) ||
-                      (use_vel && (s.fr.vel.shift || s.fr.vel.rot));
-  if (s.rg.any()) {  // (a region reads positions)
+  const bool framed = (use_pos && s.fr.pos_any()) || (use_vel && s.fr.vel.any());
+  if (use_pos && s.fr.wrap.on) {  // (the instantiations that carry the wrap's constants)
+    if (s.rg.any()) {
+      if (use_vel) launch_wrap(property_moments<true, true, true, true, true>);
+      else launch_wrap(property_moments<true, false, true, true, true>);
+    } else if (use_vel) launch_wrap(property_moments<true, true, true, false, true>);
+    else launch_wrap(property_moments<true, false, true, false, true>);
+  } else if (s.rg.any()) {  // (a region reads positions)
     if (framed) {
       if (use_vel) launch(property_moments<true, true, true, true>);
       else launch(property_moments<true, false, true, true>);
@@ -645,11 +757,18 @@ static void launch_enclosed(hipStream_t st, int grid, const Staged &s, int nt, c
   EncThresholds<NTC> th;
   for (int j = 0; j < NTC; ++j) th.t[j] = j < nt ? enc_square_bound(t[j]) : __builtin_nan("");
   auto launch = [&](auto kern) {
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(PROP_TPB), 0, st, s.pos, s.mass, s.p, s.fr, s.rg, th,
-                       want_ext, part);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(PROP_TPB), 0, st, s.pos, s.mass, s.p,
+                       s.fr.k<false>(), s.rg, th, want_ext, part);
   };
-  const bool framed = s.fr.pos.shift || s.fr.pos.rot;
-  if (s.rg.any()) {
+  auto launch_wrap = [&](auto kern) {
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(PROP_TPB), 0, st, s.pos, s.mass, s.p,
+                       s.fr.k<true>(), s.rg, th, want_ext, part);
+  };
+  const bool framed = s.fr.pos_any();
+  if (s.fr.wrap.on) {
+    if (s.rg.any()) launch_wrap(property_enclosed<NTC, true, true, true>);
+    else launch_wrap(property_enclosed<NTC, true, false, true>);
+  } else if (s.rg.any()) {
     if (framed) launch(property_enclosed<NTC, true, true>);
     else launch(property_enclosed<NTC, false, true>);
   } else if (framed) launch(property_enclosed<NTC, true, false>);
@@ -721,9 +840,8 @@ static Staged stage_scope(Device &d, hipStream_t st, const double *pos, const do
 }
 
 static void check_scope(const double *pos, int64_t n, int use_sphere, const double *sphere,
-                        const int64_t *fam, int nfam, int flags) {
-  if (flags & ~(PBX_FRAME_POS | PBX_FRAME_VEL | PBX_FRAME_ROT))
-    fail(PBX_ERR_VALUE, "flags must be a mask of PBX_FRAME_* bits (got 0x%x)", flags);
+                        const int64_t *fam, int nfam, int flags, const double *frame) {
+  (void)frame_of(flags, frame);  // (the flags and the wrap, before anything is staged)
   check_common(n, fam, nfam);
   if (use_sphere && !sphere) fail(PBX_ERR_VALUE, "use_sphere without a sphere");
   if (!pos) fail(PBX_ERR_VALUE, "pos is NULL");
@@ -745,8 +863,7 @@ int pbx_property_moments_region(const double *pos, const double *vel, const doub
                                 double *h_sums) {
   return guard([&] {
     const Region rg = region_of(nclauses, kinds, negate, params);
-    if (flags & ~(PBX_FRAME_POS | PBX_FRAME_VEL | PBX_FRAME_ROT))
-      fail(PBX_ERR_VALUE, "flags must be a mask of PBX_FRAME_* bits (got 0x%x)", flags);
+    const Frame fr = frame_of(flags, frame);  // (checks the flags and the wrap)
     if (!n_kept || !h_sums) fail(PBX_ERR_VALUE, "null output");
     check_common(n, fam, nfam);
     if (groups == 0 || (groups & ~ALL_GROUPS))
@@ -771,7 +888,7 @@ int pbx_property_moments_region(const double *pos, const double *vel, const doub
       s.p.cz = sphere[2];
       s.p.r2max = sphere[3];
     }
-    s.fr = frame_of(flags, frame);
+    s.fr = fr;
     s.rg = rg;
     run_pass(d, st, s, groups, n_kept, h_sums);
   });
@@ -854,7 +971,7 @@ int pbx_property_enclosed(const double *pos, const double *mass, int64_t n, int 
       fail(PBX_ERR_VALUE, "nt must lie in [0, %d] (got %d)", ENC_MAX, nt);
     if (nt > 0 && (!h_t || !h_msum || !h_count))
       fail(PBX_ERR_VALUE, "thresholds without h_t, h_msum or h_count");
-    check_scope(pos, n, use_sphere, sphere, fam, nfam, flags);
+    check_scope(pos, n, use_sphere, sphere, fam, nfam, flags, frame);
     Device &d = current_device();
     std::lock_guard<std::mutex> lk(d.mu);
     hipStream_t st = d.stream;
@@ -870,6 +987,42 @@ int pbx_property_enclosed(const double *pos, const double *mass, int64_t n, int 
     }
     if (h_ext)
       for (int k = 0; k < ENC_NEXT; ++k) h_ext[k] = e.ext[k];
+  });
+}
+
+int pbx_property_wrap_extents(const double *pos, int64_t n, int on_device, int flags,
+                              const double *frame, double L, double *h_ext) {
+  return guard([&] {
+    if (!h_ext) fail(PBX_ERR_VALUE, "null output");
+    if (n < 0) fail(PBX_ERR_VALUE, "negative length");
+    const Frame fr = frame_of(flags, frame);
+    if (fr.pos.rot || fr.wrap.on)
+      fail(PBX_ERR_VALUE,
+           "wrap extents are taken before a wrap and a rotation: flags may hold PBX_FRAME_POS and "
+           "PBX_FRAME_VEL only (got 0x%x)", flags);
+    if (!(L > 0.0) || L == __builtin_inf())
+      fail(PBX_ERR_VALUE, "the box size must be finite and positive (got %g)", L);
+    for (int e = 0; e < WEXT_N; ++e) h_ext[e] = (e & 1) ? -__builtin_inf() : __builtin_inf();
+    if (n == 0) return;
+    if (!pos) fail(PBX_ERR_VALUE, "pos is NULL");
+    Device &d = current_device();
+    std::lock_guard<std::mutex> lk(d.mu);
+    hipStream_t st = d.stream;
+    ScopedTimer tm("pbx.property.wrap_extents");
+    const double *dpos = stage(d, st, pos, 3, 0, n, on_device, kSlotPropPos);
+    const int grid = grid_of(n);
+    // [rows of extrema][the result]
+    double *part = (double *)d.slot(kSlotPropPart)
+                       .ensure(sizeof(double) * ((size_t)PROP_MAX_BLOCKS * WEXT_N + WEXT_N));
+    double *res = part + (size_t)PROP_MAX_BLOCKS * WEXT_N;
+    hipLaunchKernelGGL(property_wrap_extents, dim3(grid), dim3(PROP_TPB), 0, st, dpos, n, fr.pos, L,
+                       -0.5 * L, part);
+    PBX_HIP(hipGetLastError());
+    hipLaunchKernelGGL(wrap_extents_reduce, dim3(1), dim3(PROP_RG * WEXT_RCOLS), 0, st, part, grid,
+                       res);
+    PBX_HIP(hipGetLastError());
+    PBX_HIP(hipMemcpyAsync(h_ext, res, sizeof(double) * WEXT_N, hipMemcpyDeviceToHost, st));
+    PBX_HIP(hipStreamSynchronize(st));
   });
 }
 
@@ -889,7 +1042,7 @@ int pbx_property_virial_radius(const double *pos, const double *mass, int64_t n,
     if (niter_max < 1) fail(PBX_ERR_VALUE, "niter_max must be >= 1 (got %d)", niter_max);
     if (levels < 0 || levels > PBX_ENCLOSED_LEVELS)
       fail(PBX_ERR_VALUE, "levels must lie in [0, %d] (got %d)", PBX_ENCLOSED_LEVELS, levels);
-    check_scope(pos, n, use_sphere, sphere, fam, nfam, flags);
+    check_scope(pos, n, use_sphere, sphere, fam, nfam, flags, frame);
     Device &d = current_device();
     std::lock_guard<std::mutex> lk(d.mu);
     hipStream_t st = d.stream;

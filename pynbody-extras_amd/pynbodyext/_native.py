@@ -35,10 +35,12 @@ WANT_ACC = 2
 KINEMATIC_FIELDS = ("vr", "vtheta", "vphi", "vrxy", "v2", "vt")
 SRC_KIN = 16
 
-# frame flags (pbx.h PBX_FRAME_*): position shift, velocity shift, rotation
+# frame flags (pbx.h PBX_FRAME_*): position shift, velocity shift, rotation,
+# periodic wrap (bit 8 is unassigned)
 FRAME_POS = 1
 FRAME_VEL = 2
 FRAME_ROT = 4
+FRAME_WRAP = 16
 
 _LIB_NAME = "libpbx.so"
 _lib: ctypes.CDLL | None = None
@@ -186,6 +188,7 @@ _SIGNATURES: dict[str, tuple] = {
     "pbx_property_enclosed": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, _dp, _i64p, c_int,
                                       c_int, _dp, c_int, POINTER(c_int), POINTER(c_int), _dp,
                                       c_int, _dp, _i64p, _dp, _i64p, _dp]),
+    "pbx_property_wrap_extents": (c_int, [c_void_p, c_int64, c_int, c_int, _dp, c_double, _dp]),
     "pbx_property_virial_radius": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, _dp, _i64p,
                                            c_int, c_int, _dp, c_int, POINTER(c_int),
                                            POINTER(c_int), _dp, c_double, c_double, c_int, c_int,

@@ -1,8 +1,9 @@
 """Device route of the property calculators (libpbx, csrc/property.hip).
 
 Thin ctypes wrappers of pbx_property_moments(_frame, _region),
-pbx_property_shrink_center, pbx_property_enclosed and
-pbx_property_virial_radius (include/pbx.h, "scalar properties"), and the
+pbx_property_shrink_center, pbx_property_enclosed,
+pbx_property_virial_radius and pbx_property_wrap_extents (include/pbx.h,
+"scalar properties"), and the
 conditions under which a property takes them: the source is a root
 ``SimSnap`` of the snapshot layer — or a FrameView of one, whose frame then
 rides along in the pass — whose ``pos`` / ``vel`` / ``mass`` are float64 and
@@ -187,6 +188,30 @@ def virial_radius(pos, mass, *, target_rho: float, eta: float, niter_max: int = 
              nat.dptr(radius), byref(it), byref(passes), byref(kept), byref(status))
     del alive
     return float(radius[0]), it.value, passes.value, kept.value, status.value == 0
+
+
+def wrap_extents(pos, boxsize: float, *, frame=None, on_device: bool = False,
+                 n: int | None = None) -> np.ndarray:
+    """ext[12] of one streaming pass over every particle
+    (pbx_property_wrap_extents): per axis min / max of the "center" wrap and
+    min / max of the "upper" wrap of the positions in ``frame`` — which may
+    hold shifts only; a rotation or a wrap in it is a ValueError.  No
+    particles: the identities (+inf, -inf).  The choice per axis is
+    pynbodyext.frame.choose_lower."""
+    if on_device:
+        ptr, count, keep = pos, int(n), None
+    else:
+        keep = np.ascontiguousarray(np.asarray(pos), dtype=np.float64)
+        if keep.ndim != 2 or keep.shape[1] != 3:
+            raise ValueError("pos must be (N,3)")
+        ptr, count = keep.ctypes.data_as(c_void_p), keep.shape[0]
+    framed = frame is not None and not frame.empty
+    packed = frame.packed() if framed else None
+    ext = np.zeros(12)
+    nat.call("pbx_property_wrap_extents", ptr, count, int(on_device),
+             frame.flags if framed else 0, nat.dptr(packed), float(boxsize), nat.dptr(ext))
+    del keep
+    return ext
 
 
 # -- routing -------------------------------------------------------------------

@@ -1,10 +1,13 @@
 """Coordinate transformations: centre a snapshot, put it at rest, align a
-vector with z — reference pynbodyext/transforms (``WrapBox`` is not
-provided: periodic wrapping is not an affine frame and needs pynbody's box
-properties).
+vector with z — reference pynbodyext/transforms.  ``WrapBox`` (the periodic
+wrap into the box, between the shift and the rotation) lives in
+``pynbodyext.transforms.wrap``, the module the reference defines it in, and
+is imported from there: this package does not re-export it yet (DESIGN.md
+§7).
 
 Transforms never rewrite the snapshot.  A chain resolves to a frame of 15
-numbers (pynbodyext.frame) that rides along in the device passes::
+numbers, 19 with a wrap (pynbodyext.frame), that rides along in the device
+passes::
 
     krot = KappaRot().filter(Sphere(30.) & FamilyFilter("star")).transform(
         ShiftPosTo("ssc")

@@ -13,8 +13,11 @@ resolves to a :class:`~pynbodyext.frame.Frame`, step by step —
   calculator layer on a FrameView, so it takes the device routes with the
   frame so far);
 * it then extends the frame: a shift of an array not shifted yet, before
-  any rotation, sets ``c`` / ``vc``; the first rotation sets ``R``;
+  any rotation (and, for positions, before the wrap), sets ``c`` / ``vc``; a
+  wrap (transforms/wrap.py) before any rotation sets ``(L, lo)``; the first
+  rotation sets ``R``;
 * anything else — a second shift of the same array, a shift after a
+  rotation, a position shift after the wrap, a second wrap, a wrap after a
   rotation, a second rotation — materialises: ``Frame.apply`` builds a root
   snapshot in the frame so far (numpy, float64) and the chain goes on from
   it with an empty frame.  A sub-snapshot or float32 ``pos`` / ``vel`` are
@@ -105,6 +108,13 @@ class TransformBase(CalculatorBase):
         None when that is not a canonical frame."""
         raise NotImplementedError
 
+    def measure_in(self, ctx: ExecutionContext, base, frame: Frame):
+        """(base, frame, value): the step's parameter measured on ``base`` in
+        ``frame``.  A step may hand back a materialised ``base`` with an empty
+        frame when it had to measure there (a wrap after a rotation)."""
+        view = base if frame.empty else FrameView(base, frame)
+        return base, frame, self.measure(ctx, view)
+
     # -- evaluation --------------------------------------------------------------------
     def framed_sim(self, ctx: ExecutionContext, sim):
         """``sim`` in the frame this transform leads to: ``sim`` itself (an
@@ -114,8 +124,7 @@ class TransformBase(CalculatorBase):
         if not _canonical_source(base):
             base, frame = Frame().apply(sim), Frame()
         for step in self.steps():
-            view = base if frame.empty else FrameView(base, frame)
-            value = step.measure(ctx, view)
+            base, frame, value = step.measure_in(ctx, base, frame)
             nxt = step.extend(frame, value)
             if nxt is None:  # not canonical: go on from the materialised snapshot
                 base = frame.apply(base)
